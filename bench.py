@@ -19,9 +19,13 @@ Multi GPU:   python -m torch.distributed.run --nproc-per-node N bench.py --gpus 
   < r).  After the timed steps the shards' NMS lists are gathered in global slice order and ONE
   tracker on rank 0 consumes them (the C5 track merge, `track_merge`).  Weak scaling: events per
   rank fixed (--events; --preset c5 = 50 M per GPU, BASELINE config C5).
-Rank 0 prints ONE JSON line.  With the CPU leg on (default, rank 0 of a 1-GPU run), the oracle
-runs the same pipeline over exactly the step's events: that is the CPU baseline, and every GPU
-output of the step is compared with it (`parity`).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline (value, ms_per_step, config); `--dump-outputs DIR` also writes the last timed step's
+outputs as DIR/<name>.npy.  Everything beside the headline runs only with `--full`: the
+kernel-timing pass (roofline, stages), the tracker and track-merge measurements, the sharded runs'
+single-GPU rate and --dist-parity, RAW ingest, eps / DBSCAN / OPTICS, the C3 k-means, and the CPU
+leg (rank 0 of a 1-GPU run): the oracle runs the same pipeline over exactly the step's events,
+which is the CPU baseline, and every GPU output of the step is compared with it (`parity`).
 """
 from __future__ import annotations
 
@@ -100,7 +104,20 @@ def parse(argv=None):
                          "CPU) only carries the control plane (the RCCL unique id, barriers, the timing max)")
     ap.add_argument("--no-n1-rate", action="store_true",
                     help="sharded runs: skip rank 0's single-GPU rate at the same per-GPU size (per_gpu_rate_n1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the kernel-timing pass "
+                         "(roofline, per-stage and per-kernel times), the tracker and track-merge measurements, the "
+                         "sharded runs' single-GPU rate and --dist-parity, RAW ingest, eps-neighbourhoods / DBSCAN / "
+                         "OPTICS, the C3 k-means, and the CPU baseline with the full-size parity (each still subject "
+                         "to its --no-* switch).  Default: warm up, time the steps, print the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of the per-event and per-slot arrays)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dist_parity and not a.full:
+        ap.error("--dist-parity is a --full measurement: pass --full with it")
     if a.preset is None:
         a.preset = "c5" if a.gpus > 1 else "c4"
     if a.events is None:
@@ -413,7 +430,7 @@ def main():
     # the sharded timed region (the other ranks wait at the barrier), so that the line itself
     # carries the N=1 reference of its scaling efficiency
     per_gpu_rate_n1 = None
-    if dist and rank == 0 and not args.no_n1_rate:
+    if args.full and dist and rank == 0 and not args.no_n1_rate:
         for _ in range(max(1, args.warmup)):
             step_single(args.serial)
         sync_all()
@@ -469,6 +486,67 @@ def main():
         elapsed = float(tt.item())
     ms_step = elapsed / args.steps * 1e3
 
+    # what the last timed step left in the step's output buffers, before anything else runs on them
+    if args.dump_outputs:
+        dump_outputs(ecc, Path(args.dump_outputs), rank,
+                     dict(rep_xy=rep_xy, uniq=uniq, rep=rep, c=d_c, labels=labels, flags=flags, sae=sae,
+                          nms_out=nms_out[0], nms_cnt=nms_cnt[0], cap=cap))
+
+    value = world * args.steps * n / elapsed / 1e6
+    preset = next((k for k, v in PRESET_SLICES.items() if v * SLICE == n), None)
+    cname = {"c4": "BASELINE configs C2-C4", "c5": "BASELINE C5 per-GPU share"}.get(preset, "custom size")
+    if world > 1:
+        wl = (f"C5: {world}xMI355X time-window shards of a {world * n}-event stream ({n} events/GPU; "
+              f"{cname}); per shard: ")
+    else:
+        wl = ""
+    result = {
+        "metric": "Mevents/s (downsample+cluster+corner)",
+        "value": round(value, 2),
+        "unit": "Mevents/s",
+        "n_gpus": world,
+        "dist_world": dist.get_world_size() if dist else None,
+        "dist_backend": ("ecc_dist (libecc RCCL) + gloo control plane" if native is not None else args.dist_backend)
+                        if dist else None,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u16xy/i64t (int), fp32 k-means",
+        "data": "synthetic (seeded splitmix64 event generator: moving polygons + Gaussian blobs + noise)",
+        "full": bool(args.full),
+        "config": {
+            "workload": wl + f"e2e hash-downsample(8192-event windows) -> k-means k={K} ({I} iters) on reps -> "
+                             f"SAE+FAST arc corners (16384-event slices) -> 15x15 NMS; {W}x{H} sensor; "
+                             f"{n} events/GPU/step ({cname})",
+            "events_per_gpu": n, "events_total": world * n, "preset": preset,
+            "reps_per_gpu": n_reps, "width": W, "height": H, "k": K,
+            "kmeans_iters": I, "parallelism": f"time-window shards x{world}",
+            "launch": "hipGraph replay of the captured step" if graph is not None else "eager launches",
+            "streams": "two streams sharing all CUs" if not (dist or args.serial) else "see parallelism",
+            "schedule": ("pipelined: the k-means passes of step i start after its sort phase and may overlap step "
+                         "i+1's detection; the timed region ends when both streams are idle")
+                        if (pipelined and not dist and not args.serial) else "joined (per-step fork/join)",
+            "corner_shards": P,
+        },
+    }
+
+    def finish():
+        if graph is not None:
+            lib.ecc_graph_destroy(graph)
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            if native is not None:
+                native.close()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
+
+    # ---- --full: everything beside the headline --------------------------------------------------
     # 2. the kernel-timing pass: the same K steps again with HIP events recorded around every
     #    launch on its stream (ecc_ctx_set_timing) -> per-kernel average durations.  It runs on
     #    ONE stream, so that a kernel's time is its own (not queueing behind the other chain).
@@ -703,46 +781,7 @@ def main():
     if not args.no_c3 and rank == 0:
         c3_res = bench_c3(ecc, ctx, args, rep_xy, uniq, c0, K)
 
-    value = world * args.steps * n / elapsed / 1e6
-    preset = next((k for k, v in PRESET_SLICES.items() if v * SLICE == n), None)
-    cname = {"c4": "BASELINE configs C2-C4", "c5": "BASELINE C5 per-GPU share"}.get(preset, "custom size")
-    if world > 1:
-        wl = (f"C5: {world}xMI355X time-window shards of a {world * n}-event stream ({n} events/GPU; "
-              f"{cname}); per shard: ")
-    else:
-        wl = ""
-    if graph is not None:
-        lib.ecc_graph_destroy(graph)
-    result = {
-        "metric": "Mevents/s (downsample+cluster+corner)",
-        "value": round(value, 2),
-        "unit": "Mevents/s",
-        "n_gpus": world,
-        "dist_world": dist.get_world_size() if dist else None,
-        "dist_backend": ("ecc_dist (libecc RCCL) + gloo control plane" if native is not None else args.dist_backend)
-                        if dist else None,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u16xy/i64t (int), fp32 k-means",
-        "data": "synthetic (seeded splitmix64 event generator: moving polygons + Gaussian blobs + noise)",
-        "config": {
-            "workload": wl + f"e2e hash-downsample(8192-event windows) -> k-means k={K} ({I} iters) on reps -> "
-                             f"SAE+FAST arc corners (16384-event slices) -> 15x15 NMS; {W}x{H} sensor; "
-                             f"{n} events/GPU/step ({cname})",
-            "events_per_gpu": n, "events_total": world * n, "preset": preset,
-            "reps_per_gpu": n_reps, "width": W, "height": H, "k": K,
-            "kmeans_iters": I, "parallelism": f"time-window shards x{world}",
-            "launch": "hipGraph replay of the captured step" if graph is not None else "eager launches",
-            "streams": "two streams sharing all CUs" if not (dist or args.serial) else "see parallelism",
-            "schedule": ("pipelined: the k-means passes of step i start after its sort phase and may overlap step "
-                         "i+1's detection; the timed region ends when both streams are idle")
-                        if (pipelined and not dist and not args.serial) else "joined (per-step fork/join)",
-            "corner_shards": P,
-        },
+    result.update({
         "roofline": {
             "kernel": dominant, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
@@ -765,19 +804,60 @@ def main():
         "ingest": ingest,
         "eps": eps_res,
         "kmeans_c3": c3_res,
-    }
+    })
     if rank == 0 and not dist and not args.no_cpu:
         base, par = cpu_leg(ecc, args, W, H, K, I, xy_h, t_h, n, c0, ctx,
                             dict(rep_xy=rep_xy, uniq=uniq, rep=rep, c=d_c, labels=labels, flags=flags, sae=sae,
                                  nms_out=nms_out[0], nms_cnt=nms_cnt[0], cap=cap, tracker=g_tracker))
         result["cpu_baseline"] = base
         result["parity"] = par
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if dist:
-        if native is not None:
-            native.close()
-        dist.destroy_process_group()
+    finish()
+
+
+def dump_outputs(ecc, out_dir, rank, g, sample=1_500_000, seed=1):
+    """--dump-outputs: the arrays a caller of the step receives, as <name>.npy (rank r > 0:
+    <name>.rank<r>.npy), float32 / float64 only and under 64 MB in all.  Small outputs are written
+    whole; the per-event and per-slot arrays as a fixed sample (the same seeded indices in every
+    run, ascending), the corner flags' per-slice counts beside their sample.  Slots past a
+    window's count (representatives, labels) hold no output and read -1."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(seed)
+
+    def pick(total):
+        if total <= sample:
+            return np.arange(total)
+        return np.sort(rng.choice(total, sample, replace=False))
+
+    def save(name, a):
+        assert a.dtype in (np.float32, np.float64)
+        np.save(out_dir / (f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+
+    u = g["uniq"].numpy()
+    save("downsample_unique_per_window", u.astype(np.float64))
+    save("downsample_rep_per_window", g["rep"].numpy().astype(np.float64))
+    save("kmeans_centroids", g["c"].numpy().astype(np.float32))
+    save("sae", g["sae"].numpy().astype(np.float64))  # timestamps in µs: exact in float64
+    cnt = g["nms_cnt"].numpy()
+    save("nms_count_per_slice", cnt.astype(np.float64))
+    valid = (np.arange(WINDOW, dtype=np.int32)[None, :] < u[:, None]).ravel()
+    idx = pick(valid.size)
+    x, y = ecc.unpack_xy(g["rep_xy"].numpy()[idx])
+    xy = np.stack([x, y], 1).astype(np.float32)
+    xy[~valid[idx]] = -1.0
+    save("downsample_rep_xy_sample", xy)
+    lab = g["labels"].numpy()[idx].astype(np.float32)
+    lab[~valid[idx]] = -1.0
+    save("kmeans_labels_sample", lab)
+    fl = g["flags"].numpy()
+    save("corner_flags_sample", fl[pick(fl.size)].astype(np.float32))
+    save("corner_flags_per_slice", np.add.reduceat(fl.astype(np.int64), np.arange(0, fl.size, SLICE)).astype(np.float64))
+    # the NMS lists, dense in slice order (x, y, label); a sample of the rows when there are many
+    cap = g["cap"]
+    nms = g["nms_out"].numpy()
+    keep = (np.arange(cap, dtype=np.int32)[None, :] < cnt[:, None]).ravel()
+    rows = nms[keep]
+    rows = rows[pick(len(rows))]
+    save("nms_corners", np.stack([rows["x"], rows["y"], rows["label"]], 1).astype(np.float32))
 
 
 def lib_sha256(ecc):

@@ -3,7 +3,7 @@
 # Usage: ab_libs.sh <tag> <extra bench args...> -- <variant dirs...>
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" && mkdir -p gpurun_out
 TAG="$1"; shift
-ARGS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS+=("$1"); shift; done; shift
+ARGS=(--full); while [ $# -gt 0 ] && [ "$1" != "--" ]; do ARGS+=("$1"); shift; done; shift
 PKG=event-camera-clustering-and-optical-flow-estimation_amd
 for round in 1 2; do
   for v in lib "$@"; do

@@ -12,7 +12,8 @@ cp "$(find "$E/trace" -name '*kernel_stats.csv' | head -1)" $P/${T}_kernel_stats
 for f in traffic.json traffic.txt occupancy.json occupancy.txt calib.txt; do [ -f "$E/$f" ] && cp "$E/$f" $P/${T}_$f; done
 [ -f "$E/bench.json" ] && cp "$E/bench.json" $P/${T}_bench.json
 [ -f "$E/trace_bench.json" ] && cp "$E/trace_bench.json" $P/${T}_bench_under_rocprof.json
-[ -f gpurun_out/${T}_pytest.log ] && cp gpurun_out/${T}_pytest.log $P/${T}_pytest_gpu.log
+O="${ECC_OUT_DIR:-out}"   # where gpu_round.sh writes its own logs
+[ -f "$O/${T}_pytest.log" ] && cp "$O/${T}_pytest.log" $P/${T}_pytest_gpu.log
 for k in db lists; do
   D=gpurun_out/pmc_${k}_$T
   [ -d "$D" ] || continue

@@ -4,12 +4,12 @@
 #   2. FETCH_SIZE and WRITE_SIZE passes (HBM traffic, scripts/traffic.py);
 #   3. two SQ counter passes (occupancy, wait and issue fractions: scripts/pmc_summary.py);
 #   4. the FETCH_SIZE / WRITE_SIZE calibration of scripts/calib/fetch_calib (known byte counts);
-#   5. the default bench line.
+#   5. the whole bench line (bench.py --full).
 # PMC passes use --kernel-trace only (never sys/runtime traces with --pmc).
 # Usage: gpu_evidence.sh <tag> [extra bench args]      (SKIP_BENCH=1 skips step 5)
 REPO="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 TAG="${1:-r04}"; shift
-ARGS="--steps 3 --warmup 1 --no-cpu --no-tracker --no-eps --no-c3 --no-ingest --serial $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu --no-tracker --no-eps --no-c3 --no-ingest --serial $*"
 OUT="$REPO/gpurun_out/ev_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
@@ -37,5 +37,5 @@ python3 scripts/pmc_summary.py "$OUT/sq" "$OUT/occupancy.json" > "$OUT/occupancy
 [ -x scripts/calib/bin/fetch_calib ] && { python3 scripts/calib_report.py "$OUT" > "$OUT/calib.txt" || exit 1; }
 cat "$OUT/traffic.txt" "$OUT/occupancy.txt" "$OUT/calib.txt" 2>/dev/null | head -80
 [ -n "$SKIP_BENCH" ] && exit 0
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; fault $? bench
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; fault $? bench
 head -c 600 "$OUT/bench.json"

@@ -4,7 +4,7 @@
 REPO="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$REPO" && mkdir -p gpurun_out
 PKG="$REPO/event-camera-clustering-and-optical-flow-estimation_amd"
-ARGS="--steps 20 --warmup 5 --no-cpu --no-tracker --no-ingest --no-eps --no-c3"
+ARGS="--full --steps 20 --warmup 5 --no-cpu --no-tracker --no-ingest --no-eps --no-c3"
 for round in 1 2; do
   for v in lib "$@"; do
     for mode in "" --serial; do

@@ -46,7 +46,7 @@ def _run(cmd, timeout=240, port=None):
     return json.loads(lines[-1])
 
 
-COMMON = ["--steps", "2", "--warmup", "1", "--no-cpu", "--no-eps", "--no-ingest", "--no-c3", "--dist-parity"]
+COMMON = ["--full", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-eps", "--no-ingest", "--no-c3", "--dist-parity"]
 
 
 @pytest.mark.gpu
