@@ -16,9 +16,6 @@
 // Rank 0 prints one JSON line; --dump writes every rank's corner flags, final SAE and NMS lists
 // and rank 0's centroids, labels and merged tracks (tests/test_dist_native.py checks them
 // against the oracle).
-#include <sys/wait.h>
-#include <unistd.h>
-
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +24,7 @@
 #include <vector>
 
 #include "app_common.hpp"
+#include "rank_launcher.hpp"
 
 namespace {
 
@@ -254,48 +252,14 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "usage: %s --ranks N [--events n] [--steps K] [--dump DIR]\n", argv[0]);
         return 2;
     }
-    // one pipe per rank > 0: rank 0 writes the unique id into each.  Nothing here touches the GPU
-    // before the fork.
-    std::vector<int> pipes(2 * n_ranks, -1);
-    for (int r = 1; r < n_ranks; ++r)
-        if (pipe(&pipes[2 * r]) != 0) {
-            std::perror("pipe");
-            return 1;
-        }
-    std::vector<pid_t> kids;
-    for (int r = 0; r < n_ranks; ++r) {
-        const pid_t pid = fork();
-        if (pid < 0) {
-            std::perror("fork");
-            return 1;
-        }
-        if (pid == 0) {
-            uint8_t id[ECC_DIST_ID_BYTES];
-            if (r == 0) {
-                if (ecc_dist_get_unique_id(id) != ECC_OK) {
-                    std::fprintf(stderr, "ecc_dist_get_unique_id failed (librccl available: %d)\n", ecc_dist_available());
-                    _exit(1);
-                }
-                for (int q = 1; q < n_ranks; ++q)
-                    if (write(pipes[2 * q + 1], id, sizeof(id)) != (ssize_t)sizeof(id)) _exit(1);
-            } else {
-                size_t got = 0;
-                while (got < sizeof(id)) {
-                    const ssize_t k = read(pipes[2 * r], id + got, sizeof(id) - got);
-                    if (k <= 0) _exit(1);
-                    got += (size_t)k;
-                }
-            }
-            std::fflush(stdout);
-            _exit(run_rank(r, n_ranks, id, argc, argv));
-        }
-        kids.push_back(pid);
-    }
-    int rc = 0;
-    for (pid_t k : kids) {
-        int st = 0;
-        waitpid(k, &st, 0);
-        if (!WIFEXITED(st) || WEXITSTATUS(st) != 0) rc = 1;
-    }
-    return rc;
+    // the launcher forks the ranks; nothing here touches the GPU before that.  Rank 0 creates the
+    // unique id, the launcher hands it to the others and ends every rank when one fails.
+    return launch_ranks(
+        n_ranks, ECC_DIST_ID_BYTES,
+        [](uint8_t *id) {
+            if (ecc_dist_get_unique_id(id) == ECC_OK) return true;
+            std::fprintf(stderr, "ecc_dist_get_unique_id failed (librccl available: %d)\n", ecc_dist_available());
+            return false;
+        },
+        [argc, argv](int r, int n, const uint8_t *id) { return run_rank(r, n, id, argc, argv); });
 }

@@ -267,9 +267,18 @@ ECC_API int ecc_dist_gather_corners(ecc_dist *d, const ecc_corner *packed, const
         ECC_CHECK_HIP(ctx, hipMemcpyAsync(off, offsets, (size_t)(n_slices + 1) * 8, hipMemcpyDeviceToDevice, s), "offs");
     ECC_CHECK_RCCL(d, rccl().all_gather(pk, all, (size_t)t_max * 3, ncclInt32, d->comm, s), "ncclAllGather(corners)");
     ECC_CHECK_RCCL(d, rccl().all_gather(off, offs, (size_t)ns_max + 1, ncclInt64, d->comm, s), "ncclAllGather(offsets)");
-    const int64_t items = (int64_t)R * ns_max;
-    hipLaunchKernelGGL(corner_slices_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, offs, metas, R,
-                       ns_max, t_max, starts, counts);
+    return ecc_dist_corner_slices(ctx, offs, metas, R, ns_max, t_max, starts, counts, stream);
+}
+
+ECC_API int ecc_dist_corner_slices(ecc_ctx *ctx, const int64_t *offs, const int64_t *metas, int32_t n_ranks,
+                                   int64_t ns_max, int64_t t_max, int64_t *starts, int32_t *counts,
+                                   ecc_stream_t stream) {
+    if (!ctx || !offs || !metas || !starts || !counts || n_ranks < 1 || ns_max < 1 || t_max < 1) return ECC_ERR_INVALID;
+    if (ns_max > ((int64_t)0x7fffffff * 256) / n_ranks) return ECC_ERR_INVALID;  // the grid's x limit
+    ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    const int64_t items = (int64_t)n_ranks * ns_max;
+    hipLaunchKernelGGL(corner_slices_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
+                       ecc::as_stream(stream), offs, metas, n_ranks, ns_max, t_max, starts, counts);
     ECC_CHECK_LAUNCH(ctx, "corner_slices");
     return ECC_OK;
 }

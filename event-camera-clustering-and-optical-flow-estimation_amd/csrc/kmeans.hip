@@ -2343,6 +2343,13 @@ ECC_API int ecc_kmeans_labels_xy16(ecc_ctx *ctx, const uint32_t *xy, int64_t n_s
 // its cluster by ballots and per-wave counts), and wave w sums chunks w and w + 16 with each lane
 // holding the chunk's elements lane + 64 i (the tree's first four levels inside a lane, the last
 // six by shuffles).
+// A round has two barriers.  Before A, lane 0 of every wave writes the round's s_wc row, and
+// lanes 0-7 of wave 0 have added the previous round's totals to s_run.  Between A and B every
+// access to both is a read: each point's slot (s_run, the lower waves' s_wc) and the round's
+// per-cluster totals, which lanes 0-7 of wave 0 take into a register.  After B those lanes add
+// the register to s_run; nothing reads s_wc there, so a wave that runs ahead into the next
+// round (one with no point left skips the loads) may overwrite its s_wc row at once, and the
+// next round's A orders the s_run update before the next reads of it.
 constexpr int kRcThreads = 1024;
 constexpr int kRcPer = 16;                         // points per thread
 constexpr int kRcMaxPts = kRcThreads * kRcPer;     // 16384 = 8 bins of 2048
@@ -2395,7 +2402,7 @@ kmeans_refcompat_kernel(const float *__restrict__ xy, int n, float *__restrict__
                 if (c == (uint32_t)cc) rank = __popcll(m & lt);
                 if (lane == 0) s_wc[wave][cc] = __popcll(m);
             }
-            __syncthreads();
+            __syncthreads();  // A: the round's s_wc (and the previous round's s_run) are written
             if (c < 8u) {
                 int idx = s_run[c] + rank;
                 for (int w = 0; w < wave; ++w) idx += s_wc[w][c];
@@ -2404,13 +2411,13 @@ kmeans_refcompat_kernel(const float *__restrict__ xy, int n, float *__restrict__
                     bins[c * 4096 + 2048 + idx] = y;
                 }
             }
-            __syncthreads();
+            int tot = 0;  // the round's cluster totals, read while s_wc is still the round's
             if (tid < 8) {
-                int tot = 0;
 #pragma unroll
                 for (int w = 0; w < kRcThreads / 64; ++w) tot += s_wc[w][tid];
-                s_run[tid] += tot;
             }
+            __syncthreads();  // B: every read of the round's s_wc and of s_run is done
+            if (tid < 8) s_run[tid] += tot;
         }
         __syncthreads();
         // reduction_scalar: chunk sums, buf[l] += buf[l + s] for s = 512 .. 1

@@ -204,6 +204,7 @@ _sigs = {
     "ecc_dist_allreduce_f64_max": (C.c_int, [P, P, i64, P]),
     "ecc_dist_sae_handoff": (C.c_int, [P, P, i64, P, P, P]),
     "ecc_dist_gather_corners": (C.c_int, [P, P, P, i32, P, i64, P, P, i64, C.POINTER(i64), C.POINTER(i64), P]),
+    "ecc_dist_corner_slices": (C.c_int, [P, P, P, i32, i64, i64, P, P, P]),
 }
 DIST_ID_BYTES = 128
 for _name, (_res, _args) in _sigs.items():

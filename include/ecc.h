@@ -688,6 +688,20 @@ int ecc_dist_gather_corners(ecc_dist *d, const ecc_corner *packed, const int64_t
                             int32_t n_slices, ecc_corner *all, int64_t all_cap, int64_t *starts,
                             int32_t *counts, int64_t slices_cap, int64_t *n_slices_total,
                             int64_t *corners_stride, ecc_stream_t stream);
+/* The index step of ecc_dist_gather_corners on its own (no ecc_dist, no RCCL; the gather calls
+ * exactly this after its all-gathers).  All arrays DEVICE:
+ *   metas [n_ranks][2]          = {corners, slices} of rank r (ns_r = metas[2r + 1])
+ *   offs  [n_ranks][ns_max + 1] = rank r's exclusive scan of its slices' corner counts
+ *                                 (ns_r + 1 entries), zero-padded to ns_max + 1
+ * with ns_max >= every ns_r and t_max = the stride of the gathered corner lists (>= every
+ * rank's corner count), both floored at 1.  Slice s of rank r is slice k = s + the slices of
+ * the ranks below r of the global order:
+ *   starts[k] = r * t_max + offs[r][s],  counts[k] = offs[r][s + 1] - offs[r][s]
+ * for k < the sum of ns_r; nothing past that is written.  ECC_ERR_INVALID for a NULL pointer or
+ * n_ranks, ns_max or t_max < 1 (checked before the device is touched). */
+int ecc_dist_corner_slices(ecc_ctx *ctx, const int64_t *offs, const int64_t *metas, int32_t n_ranks,
+                           int64_t ns_max, int64_t t_max, int64_t *starts, int32_t *counts,
+                           ecc_stream_t stream);
 
 #ifdef __cplusplus
 }

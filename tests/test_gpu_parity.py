@@ -1274,6 +1274,85 @@ def test_kmeans_refcompat_matches_oracle(ecc, orc, gpu, case):
     assert ecc.lib.ecc_kmeans_refcompat_f32(gpu.ctx, None, 16385, d_c.ptr, 5, None, None, None, gpu.stream) == ecc.ERR_INVALID
 
 
+_RC_C0 = np.array([1, 1, 10, 10, 20, 20, 30, 30, 50, 50, 60, 60, 70, 70, 80, 80], np.float32)
+
+
+def _refcompat_points(n):
+    return (np.random.default_rng(1000 + n).random(2 * max(n, 1)) * 90).astype(np.float32)
+
+
+def _refcompat_oracle(orc, pts, n, max_passes):
+    """(passes, centroids, bin counts, chunk sums) of orc_kmeans_refcompat from _RC_C0."""
+    o_c, o_cnt, o_ss = _RC_C0.copy(), np.zeros(8, np.int32), np.zeros(32, np.float32)
+    o_p = orc.lib.orc_kmeans_refcompat(pts.ctypes.data, n, o_c.ctypes.data, max_passes, o_cnt.ctypes.data,
+                                       o_ss.ctypes.data)
+    return o_p, o_c, o_cnt, o_ss
+
+
+def _refcompat_differences(got, want):
+    """Names of the outputs (passes, centroids, bin counts, chunk sums) that differ bit for bit."""
+    names = ("passes", "centroids", "bin_counts", "chunk_sums")
+    same = (int(got[0]) == int(want[0]),
+            np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32)),
+            np.array_equal(got[2], want[2]),
+            np.array_equal(got[3].view(np.uint32), want[3].view(np.uint32)))
+    return [nm for nm, ok in zip(names, same) if not ok]
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1024, 1025, 1088, 2047, 4097, 5000, 8191, 15361, 16320, 16383,
+                               16384])
+def test_kmeans_refcompat_tail_rounds_match_oracle(ecc, orc, gpu, n):
+    """The kernel takes the points in 16 rounds of 1024 (16 waves of 64).  These sizes put the last
+    non-empty round at every shape: one lane, one wave, a wave plus a lane, a full round, a full
+    round plus a lane, 15 of 16 waves, the last round short by a lane or by a wave; after it come
+    rounds in which waves have no point.  Pass count, centroids, the last pass's bin counts and the
+    32 chunk sums equal orc_kmeans_refcompat's bit for bit.  Float inputs make the fill order of a
+    bin visible in the sums, and a bin count that shrinks from one pass to the next leaves stale
+    values past the count in the never-cleared bins (Q8), which the chunk sums include: asserted
+    on the oracle for two of the sizes, so the inputs cannot silently stop exercising it."""
+    pts, max_passes = _refcompat_points(n), 50
+    want = _refcompat_oracle(orc, pts, n, max_passes)
+    assert 1 <= want[0] <= max_passes
+    if n in (5000, 16384):
+        per_pass = [_refcompat_oracle(orc, pts, n, m)[2] for m in range(1, want[0] + 1)]
+        assert any((b < a).any() for a, b in zip(per_pass[:-1], per_pass[1:])), per_pass
+    d_pts, d_c = dev(ecc, pts), dev(ecc, _RC_C0)
+    d_p, d_cnt, d_ss = ecc.DeviceArray(1, np.int32), ecc.DeviceArray(8, np.int32), ecc.DeviceArray(32, np.float32)
+    ecc.check(ecc.lib.ecc_kmeans_refcompat_f32(gpu.ctx, d_pts.ptr, n, d_c.ptr, max_passes, d_p.ptr, d_cnt.ptr, d_ss.ptr,
+                                               gpu.stream))
+    gpu.sync()
+    got = (d_p.numpy()[0], d_c.numpy(), d_cnt.numpy(), d_ss.numpy())
+    assert not _refcompat_differences(got, want), (got, want)
+
+
+@pytest.mark.parametrize("n", [3, 1025, 5000, 15361])
+def test_kmeans_refcompat_is_deterministic(ecc, orc, gpu, n):
+    """50 launches on the same buffers (centroids reset before each), every one equal to the
+    oracle's result, computed once.  The sizes are those whose last non-empty round is followed by
+    rounds in which whole waves have no point and run ahead of the others, which is where an
+    unordered access to the per-wave counts would show.  Repetition can expose a race; it cannot
+    prove there is none: correctness rests on the barrier structure stated above
+    kmeans_refcompat_kernel (every access to s_wc and s_run between a round's two barriers is a
+    read; the writes come after the second and before the next round's first)."""
+    pts, max_passes, launches = _refcompat_points(n), 50, 50
+    want = _refcompat_oracle(orc, pts, n, max_passes)
+    d_pts, d_c = dev(ecc, pts), ecc.DeviceArray(16, np.float32)
+    d_p, d_cnt, d_ss = ecc.DeviceArray(1, np.int32), ecc.DeviceArray(8, np.int32), ecc.DeviceArray(32, np.float32)
+    differing = {}
+    for i in range(launches):
+        d_c.copy_from(_RC_C0, gpu.stream)
+        ecc.check(ecc.lib.ecc_kmeans_refcompat_f32(gpu.ctx, d_pts.ptr, n, d_c.ptr, max_passes, d_p.ptr, d_cnt.ptr,
+                                                   d_ss.ptr, gpu.stream))
+        gpu.sync()
+        got = (d_p.numpy(gpu.stream)[0], d_c.numpy(gpu.stream), d_cnt.numpy(gpu.stream), d_ss.numpy(gpu.stream))
+        gpu.sync()
+        diff = _refcompat_differences(got, want)
+        if diff:
+            differing[i] = diff
+    print(f"refcompat determinism n={n}: {len(differing)} of {launches} launches differ from the oracle")
+    assert not differing, differing
+
+
 @pytest.mark.parametrize("engine", [1, 2, 3])
 def test_kmeans_c3_f32_50m(ecc, gpu, c3_points, engine):
     pts, c0, o_c, o_lab, o_it = c3_points
