@@ -1,7 +1,9 @@
 // Host program mirroring OPT/test/cluster_event_data.cpp (clustering_test_1 :429-545): read the
 // (x,y) of an event CSV, optics::compute_reachability_dists(points, min_pts = 2, eps = 10)
 // (:449), get_cluster_indices(reach, 10) (:454), and print each cluster's size, centroid and
-// variance (:470-530).  eps-neighbourhoods/core distances on the GPU, ordering on the host.
+// variance (:470-530).  eps-neighbourhoods/core distances on the GPU, ordering on the host; with
+// --device-order (at most 8192 points) the ordering runs on the GPU too and prints the same.
+#include <algorithm>
 #include <cmath>
 
 #include "app_common.hpp"
@@ -17,6 +19,34 @@ static std::vector<std::array<int, 2>> read_points(const char *path) {
     return pts;
 }
 
+// The points as one segment of packed u16 xy (translated to the bounding box's corner: distances
+// do not change) through ecc::optics::compute_reachability_dists_windows.
+static std::vector<ecc::optics::reachability_dist> device_order(const std::vector<std::array<int, 2>> &pts,
+                                                                size_t min_pts, double eps) {
+    if (pts.empty()) return {};
+    if (pts.size() > 8192) {
+        std::fprintf(stderr, "--device-order: %zu points, one device segment holds at most 8192\n", pts.size());
+        std::exit(1);
+    }
+    if (eps <= 0.0) eps = ecc::optics::epsilon_estimation(pts, min_pts);
+    int xmn = pts[0][0], ymn = pts[0][1], xmx = xmn, ymx = ymn;
+    for (const auto &p : pts) {
+        xmn = std::min(xmn, p[0]); xmx = std::max(xmx, p[0]);
+        ymn = std::min(ymn, p[1]); ymx = std::max(ymx, p[1]);
+    }
+    if ((int64_t)xmx - xmn > 65535 || (int64_t)ymx - ymn > 65535) {
+        std::fprintf(stderr, "--device-order: the points span more than 65535 on an axis\n");
+        std::exit(1);
+    }
+    std::vector<uint32_t> xy(pts.size());
+    for (size_t i = 0; i < pts.size(); ++i) xy[i] = ecc::pack_xy(pts[i][0] - xmn, pts[i][1] - ymn);
+    ecc::Context &ctx = ecc::Context::default_context();
+    ecc::DeviceBuffer d_xy;
+    d_xy.upload(xy.data(), xy.size() * 4, ctx.stream());
+    return ecc::optics::compute_reachability_dists_windows(ctx, d_xy.as<uint32_t>(), 1, (int64_t)pts.size(), nullptr,
+                                                           min_pts, eps)[0];
+}
+
 int main(int argc, char **argv) {
     try {
         std::vector<std::array<int, 2>> pts;
@@ -30,7 +60,9 @@ int main(int argc, char **argv) {
         const size_t min_pts = (size_t)opt_int(argc, argv, "--min-pts", 2);
         const double eps = opt_int(argc, argv, "--eps", 10), thr = opt_int(argc, argv, "--threshold", 10);
         // --eps 0 or negative: estimated (optics.hpp:428-430)
-        auto reach = ecc::optics::compute_reachability_dists(pts, min_pts, eps);
+        // --device-order: the whole ordering on the GPU, the points as one ecc_optics_grid segment
+        auto reach = has_flag(argc, argv, "--device-order") ? device_order(pts, min_pts, eps)
+                                                            : ecc::optics::compute_reachability_dists(pts, min_pts, eps);
         auto clusters = ecc::optics::get_cluster_indices(reach, thr);
         std::printf("points %zu clusters %zu\n", pts.size(), clusters.size());
         for (size_t c = 0; c < clusters.size(); ++c) {

@@ -193,6 +193,8 @@ _sigs = {
     "ecc_dbscan_extract": (C.c_int, [P, i64, i64, P, P, P, i64, i32, i32, i32, P, P, P, i64, P, P]),
     "ecc_dbscan_grid": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, i32, i32, P, P, P, i64, P, P]),
     "ecc_dbscan_status": (C.c_int, [P, P]),
+    "ecc_optics_grid": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, C.c_double, P, P, P, P, P]),
+    "ecc_optics_grid_status": (C.c_int, [P, P]),
     "ecc_device_sync": (C.c_int, []),
     "ecc_reslice_n_us": (C.c_int, [P, P, i64, i64, P, i64, P, P]),
     "ecc_dist_available": (C.c_int, []),
@@ -510,6 +512,18 @@ class Context:
 
     def dbscan_status(self) -> int:
         return lib.ecc_dbscan_status(self.ctx, self.stream)
+
+    def optics_grid(self, xy: DeviceArray, n_segs: int, stride: int, counts_in, eps: float, min_pts: int,
+                    threshold: float, order: DeviceArray, reach: DeviceArray, cluster: DeviceArray | None = None,
+                    n_clusters: DeviceArray | None = None):
+        """OPTICS ordering (order int32, reach float64, indexed s * stride + i) and, when cluster /
+        n_clusters are given, the threshold clusters of every segment in one launch."""
+        check(lib.ecc_optics_grid(self.ctx, xy.ptr, n_segs, stride, _ptr(counts_in), eps, min_pts, threshold,
+                                  order.ptr, reach.ptr, _ptr(cluster), _ptr(n_clusters), self.stream),
+              "ecc_optics_grid")
+
+    def optics_grid_status(self) -> int:
+        return lib.ecc_optics_grid_status(self.ctx, self.stream)
 
     # ---- 8. RAW ingest
     def evt_decode(self, fmt: int, words: DeviceArray, n_words: int, xy: DeviceArray | None,

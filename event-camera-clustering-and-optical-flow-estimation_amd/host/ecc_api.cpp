@@ -626,6 +626,35 @@ std::vector<reachability_dist> compute_reachability_dists(const std::vector<std:
     return optics_points(Context::default_context(), points, min_pts, epsilon);
 }
 
+std::vector<std::vector<reachability_dist>> compute_reachability_dists_windows(
+    Context &ctx, const uint32_t *device_xy, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
+    std::size_t min_pts, double epsilon) {
+    if (n_segs < 0 || min_pts > 64) throw Error(ECC_ERR_INVALID, "compute_reachability_dists_windows");
+    std::vector<std::vector<reachability_dist>> result((size_t)n_segs);
+    if (n_segs == 0) return result;
+    ecc_stream_t s = ctx.stream();
+    const size_t n = (size_t)n_segs * (size_t)std::max<int64_t>(seg_stride, 0);
+    DeviceBuffer d_order(std::max<size_t>(n, 1) * 4), d_reach(std::max<size_t>(n, 1) * 8);
+    check(ecc_optics_grid(ctx.get(), device_xy, n_segs, seg_stride, device_seg_counts, epsilon, (int32_t)min_pts, 0.0,
+                          d_order.as<int32_t>(), d_reach.as<double>(), nullptr, nullptr, s),
+          "ecc_optics_grid");
+    std::vector<int32_t> order(n), counts((size_t)n_segs, (int32_t)seg_stride);
+    std::vector<double> reach(n);
+    d_order.download(order.data(), n * 4, s);
+    d_reach.download(reach.data(), n * 8, s);
+    if (device_seg_counts) check(ecc_memcpy_d2h(counts.data(), device_seg_counts, (size_t)n_segs * 4, s), "read seg_counts");
+    ctx.sync();
+    check(ecc_optics_grid_status(ctx.get(), s), "ecc_optics_grid");
+    for (int64_t g = 0; g < n_segs; ++g) {
+        const int64_t m = std::min<int64_t>(std::max<int32_t>(counts[(size_t)g], 0), seg_stride);
+        result[(size_t)g].reserve((size_t)m);
+        for (int64_t i = 0; i < m; ++i)
+            result[(size_t)g].emplace_back((std::size_t)order[(size_t)(g * seg_stride + i)],
+                                           reach[(size_t)(g * seg_stride + i)]);
+    }
+    return result;
+}
+
 std::vector<std::vector<std::size_t>> get_cluster_indices(const std::vector<reachability_dist> &rd,
                                                           double thr) {  // optics.hpp:674-690
     std::vector<std::vector<std::size_t>> result;

@@ -530,6 +530,38 @@ int ecc_dbscan_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int64_t se
                     int64_t dup_cap, int64_t *n_dups, ecc_stream_t stream);
 int ecc_dbscan_status(ecc_ctx *ctx, ecc_stream_t stream);
 
+/* ecc_optics_grid: the OPTICS ordering of every segment, and optionally its threshold clusters,
+ * in one launch (one workgroup per segment; the same segment conventions as ecc_dbscan_grid,
+ * seg_stride <= 8192, seg_counts NULL = full segments, duplicates allowed).
+ * Reference: optics::compute_reachability_dists with exact eps-balls — core distances
+ *   OPT/include/optics/optics.hpp:286-299, reachability update :315-337 (286-337), ordered
+ *   seed-set expansion :525-555 — and get_cluster_indices :674-690, with the parameters of the
+ *   reference's event driver OPT/test/cluster_event_data.cpp:449-454 (min_pts 2, eps 10,
+ *   threshold 10) as the workload.
+ * Integer coordinates make every d^2 an exact integer and reach = sqrt(max(core^2, d^2)), so the
+ * expansion runs on the integer keys (reach^2, index) — the order of optics.hpp:67-69 — and the
+ * outputs are bit-exact: fp64 appears only as sqrt((double)reach^2) and in the threshold test.
+ * Outputs for segment s, i < seg_counts[s] (arrays indexed s*seg_stride + i; entries with
+ * i >= seg_counts[s] are left untouched):
+ *   order[..]   = segment-local index of the i-th ordered point;
+ *   reach[..]   = its reachability distance, -1 when undefined;
+ *   cluster[..] = id of the threshold cluster the i-th ordered point falls in: the running count
+ *                 of entries with reach < 0 || reach >= threshold (compared in fp64), minus 1,
+ *                 clamped at 0 (get_cluster_indices' push_back / back().push_back);
+ *   n_clusters[s] = that count (0 for an empty segment).
+ * cluster and n_clusters are both NULL (no threshold pass) or both set.
+ * ECC_ERR_INVALID (before any launch): NULL ctx; NULL xy / order / reach with n_segs > 0;
+ * seg_stride outside [1, 8192]; eps <= 0, eps > 32767 or not finite; min_pts outside [1, 64]
+ * (ecc_eps_counts' core-distance range); only one of cluster / n_clusters.  The reference's
+ * eps <= 0 -> epsilon_estimation (:428-430) stays with ecc_optics_f64.
+ * ecc_optics_grid_status: always ECC_OK for a valid ctx — the seed set holds every unprocessed
+ * point at most once, so the kernel has no capacity that can overflow (does not synchronise). */
+int ecc_optics_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int64_t seg_stride,
+                    const int32_t *seg_counts, double eps, int32_t min_pts, double threshold,
+                    int32_t *order, double *reach, int32_t *cluster, int32_t *n_clusters,
+                    ecc_stream_t stream);
+int ecc_optics_grid_status(ecc_ctx *ctx, ecc_stream_t stream);
+
 /* DBSCAN over ONE point cloud of any size in 1-3 dimensions: DBSCANSimpleCluster::extract
  * (PCC/DBSCAN_simple.h:27-90) with its radiusSearch (:118-142) on the reference's own input type,
  * a float pcl::PointXYZ cloud (ecc_dbscan_cloud_f32, dim 3 = x,y,z; the differences in float as

@@ -410,6 +410,14 @@ std::vector<reachability_dist> compute_reachability_dists(
 std::vector<reachability_dist> optics_f64_export(ecc_ctx *ctx, ecc_stream_t s, const double *pts, int64_t n, int D,
                                                  std::size_t min_pts, double epsilon);
 
+// The same ordering for many independent windows of packed u16 xy points already on the DEVICE
+// (ecc_optics_grid: the whole expansion on the GPU, one launch for all segments; seg_stride
+// <= 8192, device_seg_counts null = full segments, epsilon in (0, 32767], min_pts in [1, 64]).
+// One vector per segment, point_index local to the segment.  Synchronises the context's stream.
+std::vector<std::vector<reachability_dist>> compute_reachability_dists_windows(
+    Context &ctx, const uint32_t *device_xy, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
+    std::size_t min_pts, double epsilon);
+
 template <typename T, std::size_t dimension>
 double epsilon_estimation(const std::vector<std::array<T, dimension>> &points, std::size_t min_pts);
 
