@@ -13,11 +13,14 @@
 //
 // Grid: cells of eps * (1 + 1e-6) (|p - q| <= eps keeps floor((p - mn) / cs) within one cell
 // despite the rounding of the fp32 difference, <= 2^-24 relative), doubled until at most
-// max_cells cells.  Points are counting-sorted by cell into SoA arrays (sc[d * n + k]) with
-// their original indices (sidx[k]); a query walks the 3^(D-1) contiguous runs of its 3^D cells.
+// max_cells cells; the arithmetic, its bound and what a box too wide for a double gets are in
+// grid_geometry.hpp (host-callable).  Points are counting-sorted by cell into SoA arrays
+// (sc[d * n + k]) with their original indices (sidx[k]); a query walks the 3^(D-1) contiguous
+// runs of its 3^D cells.
 #pragma once
 
 #include "ecc_internal.hpp"
+#include "grid_geometry.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,14 +31,6 @@ namespace rgrid {
 constexpr int kThreads = 256;
 constexpr int kGridWord = 16;  // ctx->flags[16..]: bounding-box keys, then the grid geometry
 constexpr int kBadWord = 7;    // ctx->flags[7]: bit 1 = a non-finite coordinate was seen (radius status)
-
-struct Grid {
-    double mn[3];
-    double cs;
-    int64_t dims[3];
-    int64_t n_cells;
-    int dim;
-};
 
 // order-preserving int64 key of a double (and back)
 __device__ __forceinline__ int64_t dkey(double v) {
@@ -99,42 +94,12 @@ bbox_kernel(const T *__restrict__ pts, int64_t n, int dim, int64_t *keys, int32_
         }
 }
 
+// one lane: the bounded sizing loop of grid_geometry.hpp over the box the keys hold
 static __global__ void grid_setup_kernel(const int64_t *keys, int dim, double eps, int64_t max_cells, Grid *g) {
     if (threadIdx.x != 0) return;
-    Grid r{};
-    r.dim = dim;
-    double cs = eps > 0.0 ? eps * (1.0 + 1e-6) : 1.0;
-    double span[3] = {0.0, 0.0, 0.0};
-    for (int d = 0; d < dim; ++d) {
-        r.mn[d] = dval(keys[d]);
-        span[d] = dval(keys[3 + d]) - r.mn[d];
-        if (!(span[d] >= 0.0)) span[d] = 0.0;  // no finite point at all: one cell
-    }
-    for (;;) {
-        int64_t cells = 1;
-        bool ok = true;
-        for (int d = 0; d < dim; ++d) {
-            const double c = floor(span[d] / cs) + 1.0;
-            if (!(c < 4.0e18)) { ok = false; break; }
-            r.dims[d] = (int64_t)c;
-            if (cells > max_cells / r.dims[d] + 1) { ok = false; break; }
-            cells *= r.dims[d];
-        }
-        if (ok && cells <= max_cells) {
-            r.n_cells = cells;
-            break;
-        }
-        cs *= 2.0;
-    }
-    for (int d = dim; d < 3; ++d) r.dims[d] = 1;
-    r.cs = cs;
-    *g = r;
-}
-
-__device__ __forceinline__ int64_t cell_coord(double v, double mn, double cs, int64_t dims) {
-    const double f = floor((v - mn) / cs);
-    if (!(f >= 0.0)) return 0;  // also NaN
-    return f >= (double)dims ? dims - 1 : (int64_t)f;
+    const double mn[3] = {dval(keys[0]), dval(keys[1]), dval(keys[2])};
+    const double mx[3] = {dval(keys[3]), dval(keys[4]), dval(keys[5])};
+    *g = grid_geometry(mn, mx, dim, eps, max_cells);
 }
 
 template <typename T>

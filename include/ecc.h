@@ -461,7 +461,14 @@ int ecc_eps_total(ecc_ctx *ctx, const int64_t *offsets, int64_t n, int64_t *tota
  * ball's indices in grid order (the OPTICS expansion does not depend on it) and, when nbr_dist
  * is not NULL, their distances sqrt(square_distance) (geom::dist, optics.hpp:326);
  * ecc_radius_status reports ECC_ERR_CAPACITY if nbr_cap was too small.  Deterministic counts
- * and core distances. */
+ * and core distances.
+ * Any finite coordinates and any finite eps >= 0 are served, and the result is always the brute
+ * force's: where an axis' max - min overflows a double (say -1e308 and 1e308) the grid is sized
+ * for DBL_MAX and the far end shares its last cell; a pair whose per-axis difference overflows
+ * has square_distance = +inf and is no neighbour, unless eps * eps is +inf as well (eps above
+ * about 1.3e154), when every pair of finite points is one (`inf <= inf`) and the grid is a single
+ * cell.  Far outliers cost speed, not correctness: the cell doubles until at most max(4 n, 4096)
+ * cells cover the box, so the bulk of the points may share a few cells. */
 int ecc_radius_counts_f64(ecc_ctx *ctx, const double *pts, int64_t n, int32_t dim, double eps,
                           int32_t min_pts, int32_t *counts, double *core_dist, ecc_stream_t stream);
 int ecc_radius_lists_f64(ecc_ctx *ctx, const double *pts, int64_t n, int32_t dim, double eps,
@@ -489,7 +496,8 @@ int ecc_lists_sort_ascending(ecc_ctx *ctx, int64_t n, const int64_t *offsets, in
 /* OPTICS ordering (optics::compute_reachability_dists, optics.hpp:413-565): HOST pts[n*dim]
  * (dim 1-3) in; the GPU radius search above, then the ordered seed-set expansion on the host.
  * eps <= 0: epsilon_estimation (:369-387).  order[i] = point index of the i-th ordered point,
- * reach[i] = its reachability (-1 undefined).  Synchronises `stream`. */
+ * reach[i] = its reachability (-1 undefined).  Synchronises `stream`.  Huge-span input as for
+ * ecc_radius_counts_f64. */
 int ecc_optics_f64(ecc_ctx *ctx, const double *pts, int64_t n, int32_t dim, int32_t min_pts, double eps,
                    int64_t *order, double *reach, ecc_stream_t stream);
 
@@ -570,7 +578,9 @@ int ecc_optics_grid_status(ecc_ctx *ctx, ecc_stream_t stream);
  * [n*dim].  A negative eps acts as |eps| (radius_square = radius*radius, :127).  Outputs as
  * ecc_dbscan_extract for a single segment: labels[n] (cluster index in output order or -1),
  * *n_clusters (device int32), dups / *n_dups (device) further memberships.  No size cap and no
- * component cap (global union-find, clusters ordered by a device radix sort).
+ * component cap (global union-find, clusters ordered by a device radix sort).  Coordinates
+ * whose span overflows a double, and an eps whose square does, are served as by
+ * ecc_radius_counts_f64 (the same grid): the clusters are the brute-force radiusSearch's.
  * ecc_dbscan_cloud_status: ECC_ERR_CAPACITY if dups overflowed (*n_dups holds the number needed),
  * ECC_ERR_INVALID if a coordinate was not finite. */
 int ecc_dbscan_cloud_f32(ecc_ctx *ctx, const float *pts, int64_t n, int32_t dim, double eps,
