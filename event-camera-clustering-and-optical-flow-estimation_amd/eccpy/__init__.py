@@ -195,6 +195,10 @@ _sigs = {
     "ecc_dbscan_status": (C.c_int, [P, P]),
     "ecc_optics_grid": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, C.c_double, P, P, P, P, P]),
     "ecc_optics_grid_status": (C.c_int, [P, P]),
+    "ecc_optics_xi": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, C.c_double, P, i64, P, P]),
+    "ecc_optics_xi_status": (C.c_int, [P, P]),
+    "ecc_optics_xi_resident_segments": (C.c_int, [P, P]),
+    "ecc_optics_xi_host": (C.c_int, [P, i64, C.c_double, i32, C.c_double, P, i64, P]),
     "ecc_device_sync": (C.c_int, []),
     "ecc_reslice_n_us": (C.c_int, [P, P, i64, i64, P, i64, P, P]),
     "ecc_dist_available": (C.c_int, []),
@@ -525,6 +529,22 @@ class Context:
     def optics_grid_status(self) -> int:
         return lib.ecc_optics_grid_status(self.ctx, self.stream)
 
+    def optics_xi(self, reach: DeviceArray, n_segs: int, stride: int, counts_in, chi: float, min_pts: int,
+                  steep_area_min_diff: float, clusters: DeviceArray, cap: int, n_clusters: DeviceArray):
+        """xi clusters of every segment's reachability plot (reach float64 as optics_grid writes it) in
+        one launch: clusters int32[n_segs * cap * 2] as {begin, end} pairs, n_clusters int32[n_segs]."""
+        check(lib.ecc_optics_xi(self.ctx, reach.ptr, n_segs, stride, _ptr(counts_in), chi, min_pts,
+                                steep_area_min_diff, clusters.ptr, cap, n_clusters.ptr, self.stream), "ecc_optics_xi")
+
+    def optics_xi_status(self) -> int:
+        return lib.ecc_optics_xi_status(self.ctx, self.stream)
+
+    def optics_xi_resident_segments(self) -> int:
+        """Segments (waves) of the xi kernel one compute unit holds at once (occupancy query)."""
+        v = C.c_int32(0)
+        check(lib.ecc_optics_xi_resident_segments(self.ctx, C.addressof(v)), "ecc_optics_xi_resident_segments")
+        return v.value
+
     # ---- 8. RAW ingest
     def evt_decode(self, fmt: int, words: DeviceArray, n_words: int, xy: DeviceArray | None,
                    t: DeviceArray | None, p: DeviceArray | None, cap: int, n_out: DeviceArray,
@@ -729,6 +749,22 @@ def evt_encode(fmt: int, xy, t, p) -> np.ndarray:
     if k < 0:
         raise EccError(int(k), "evt_encode")
     return out[:k].copy()
+
+
+def optics_xi_host(reach, chi: float, min_pts: int, steep_area_min_diff: float = 0.0, cap: int | None = None):
+    """xi clusters of one host reachability plot (no GPU): int32 array (k, 2) of {begin, end} pairs.
+    With cap, at most cap pairs and ERR_CAPACITY raised when there are more."""
+    r = np.ascontiguousarray(reach, np.float64)
+    n_out = C.c_int64(0)
+    if cap is None:  # count, then fetch
+        rc = lib.ecc_optics_xi_host(r.ctypes.data, r.size, chi, min_pts, steep_area_min_diff, None, 0, C.addressof(n_out))
+        if rc not in (OK, ERR_CAPACITY):
+            check(rc, "ecc_optics_xi_host")
+        cap = n_out.value
+    out = np.zeros((max(cap, 1), 2), np.int32)
+    check(lib.ecc_optics_xi_host(r.ctypes.data, r.size, chi, min_pts, steep_area_min_diff, out.ctypes.data, cap,
+                                 C.addressof(n_out)), "ecc_optics_xi_host")
+    return out[:n_out.value]
 
 
 def pack_xy(x, y) -> np.ndarray:

@@ -570,6 +570,42 @@ int ecc_optics_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int64_t se
                     ecc_stream_t stream);
 int ecc_optics_grid_status(ecc_ctx *ctx, ecc_stream_t stream);
 
+/* ecc_optics_xi: the xi ("chi") extraction of nested clusters from the reachability plot of every
+ * segment, in one launch (a wave per segment; LDS does not grow with seg_stride).
+ * Reference: optics::get_chi_clusters_flat OPT/include/optics/optics.hpp:803-944, the literal loop
+ *   (:814-944) in fp64 with the reference's expressions and operation order; pairs in its push
+ *   order (by steep-up area, then by position in the SDA list).
+ * reach: DEVICE fp64, reach[s*seg_stride + i] for i < seg_counts[s], a negative value = undefined:
+ *   exactly what ecc_optics_grid and ecc_optics_f64 write.  seg_counts NULL = full segments;
+ *   1 <= seg_stride <= INT32_MAX.
+ * clusters: DEVICE int32[n_segs * cap * 2]; segment s's pair k at (s*cap + k) * 2 as {begin, end},
+ *   positions in the ordered plot, inclusive.  n_clusters[s] = the number of pairs segment s has,
+ *   even above cap; only the first cap are written and nothing else of `clusters` is touched.
+ * geom::in_range(a, b, range) (:875, not in the reference tree) is |a - b| <= range; a segment of
+ * fewer than 2 points has no clusters (the reference's n - 2 wraps).  NaN or infinite reach values
+ * give an unspecified result for that segment, inside the segment's outputs.
+ * Uses the context workspace (grown on the first call: not inside a stream capture).
+ * ECC_ERR_INVALID (before any launch): NULL ctx; NULL reach / clusters / n_clusters with
+ * n_segs > 0; n_segs < 0; cap < 0; seg_stride out of range; chi not finite or outside (0, 1);
+ * steep_area_min_diff not finite or outside [0, 1); min_pts < 2 (the reference's min_pts - 2
+ * wraps).  n_segs == 0: ECC_OK after the same range checks.
+ * ecc_optics_xi_status (optics.hpp:803-944): synchronises `stream`; ECC_ERR_CAPACITY if a segment
+ * of the last call had more pairs than cap; ECC_ERR_INVALID for NULL ctx. */
+int ecc_optics_xi(ecc_ctx *ctx, const double *reach, int64_t n_segs, int64_t seg_stride,
+                  const int32_t *seg_counts, double chi, int32_t min_pts, double steep_area_min_diff,
+                  int32_t *clusters, int64_t cap, int32_t *n_clusters, ecc_stream_t stream);
+int ecc_optics_xi_status(ecc_ctx *ctx, ecc_stream_t stream);
+/* *per_cu = the segments (waves) of ecc_optics_xi's kernel that one compute unit holds at once: the
+ * runtime's occupancy query for the kernel as built.  ECC_ERR_INVALID: NULL ctx or per_cu. */
+int ecc_optics_xi_resident_segments(ecc_ctx *ctx, int32_t *per_cu);
+/* ecc_optics_xi_host (optics.hpp:803-944): the same extraction for ONE plot in HOST memory, of any
+ * n <= INT32_MAX, on the host (no GPU, no context): the route for a single ecc_optics_f64 result.
+ * clusters: HOST int32[cap * 2]; *n_out = the number of pairs; only cap are written, and the
+ * return is then ECC_ERR_CAPACITY.  ECC_ERR_INVALID: the parameter ranges of ecc_optics_xi, n < 0,
+ * cap < 0, NULL n_out, NULL reach with n > 0, NULL clusters with cap > 0. */
+int ecc_optics_xi_host(const double *reach, int64_t n, double chi, int32_t min_pts,
+                       double steep_area_min_diff, int32_t *clusters, int64_t cap, int64_t *n_out);
+
 /* DBSCAN over ONE point cloud of any size in 1-3 dimensions: DBSCANSimpleCluster::extract
  * (PCC/DBSCAN_simple.h:27-90) with its radiusSearch (:118-142) on the reference's own input type,
  * a float pcl::PointXYZ cloud (ecc_dbscan_cloud_f32, dim 3 = x,y,z; the differences in float as

@@ -12,6 +12,7 @@
 //   optics::compute_reachability_dists<N>(pts, min_pts, eps)
 //                                    OPT/include/optics/optics.hpp:413-565  ecc::optics::compute_reachability_dists
 //                                                                  (runtime N instead of the template N)
+//   optics::get_chi_clusters_flat    optics.hpp:803-944             ecc::optics::get_chi_clusters_flat[_windows]
 //   optics::get_cluster_indices / epsilon_estimation
 //                                    optics.hpp:674-690, 369-387   ecc::optics::...
 //   DBSCANSimpleCluster / DBSCANPrecompCluster::{setInputCloud, setClusterTolerance,
@@ -423,6 +424,19 @@ double epsilon_estimation(const std::vector<std::array<T, dimension>> &points, s
 
 std::vector<std::vector<std::size_t>> get_cluster_indices(
     const std::vector<reachability_dist> &reach_dists, double reachability_threshold);
+
+// optics.hpp:803-944 — the xi ("chi") extraction of nested clusters from a reachability plot:
+// (begin, end) positions in the ordered plot, inclusive, in the reference's push order
+// (ecc_optics_xi_host; no GPU).  chi in (0, 1), steep_area_min_diff in [0, 1), min_pts >= 2.
+std::vector<std::pair<std::size_t, std::size_t>> get_chi_clusters_flat(
+    const std::vector<reachability_dist> &reach_dists, double chi, std::size_t min_pts,
+    double steep_area_min_diff = 0.0);
+// The same for many plots already on the DEVICE, laid out as ecc_optics_grid writes `reach`
+// (ecc_optics_xi: one launch for all segments, any seg_stride; device_seg_counts null = full
+// segments).  One vector of pairs per segment.  Synchronises the context's stream.
+std::vector<std::vector<std::pair<std::size_t, std::size_t>>> get_chi_clusters_flat_windows(
+    Context &ctx, const double *device_reach, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
+    double chi, std::size_t min_pts, double steep_area_min_diff = 0.0);
 
 }  // namespace optics
 
