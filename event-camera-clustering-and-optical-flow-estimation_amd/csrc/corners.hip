@@ -102,6 +102,17 @@ __device__ __forceinline__ void tile_origin(const CornerGeom &g, int tile, int &
     y0 = (tile / g.tiles_x) * kTile;
 }
 
+// The reference compares the two streak-end neighbours as int64 but scans the arc in double
+// (FCT/…group_track.cpp:977-990, :1024-1036).  Below 2^53 ticks the conversion is exact and the
+// whole test is an integer one; from 2^53 upward neighbouring timestamps round together and
+// `tj >= min_t` can hold in double where it does not in int64.  A group that reaches that range is
+// therefore never narrow: every test of it takes the exact path, which orders the values as the
+// reference's doubles do (double_key).  No stream below 2^53 changes path.
+constexpr int64_t kDoubleExact = (int64_t)1 << 53;
+__device__ __forceinline__ bool beyond_double(int64_t t_first, int64_t t_last) {
+    return t_last >= kDoubleExact || t_first <= -kDoubleExact;
+}
+
 // The group's events span < 2^32 - 1 ticks: t - t(first event) fits a u32 (+1 still fits).
 __device__ __forceinline__ bool group_narrow(const int64_t *__restrict__ t, const CornerGeom &g, int64_t grp,
                                              int64_t *t_first) {
@@ -120,7 +131,9 @@ __device__ __forceinline__ bool group_fmt4(const int64_t *__restrict__ t, const 
     const int64_t first = grp * kGroup * (int64_t)g.S;
     const int64_t end = (grp + 1) * kGroup * (int64_t)g.S;
     if (g.any_order) return false;
-    return (uint64_t)(t[(end < g.n ? end : g.n) - 1] - t[first]) < 0xFFFFFFull;
+    const int64_t t_first = t[first], t_last = t[(end < g.n ? end : g.n) - 1];
+    if (beyond_double(t_first, t_last)) return false;  // wide (group_ref): the keys keep the event index
+    return (uint64_t)(t_last - t_first) < 0xFFFFFFull;
 }
 
 // floor(el / S) for el < 2^24 (float estimate, then exact correction).
@@ -388,7 +401,8 @@ __device__ __forceinline__ GroupRef group_ref(const int64_t *__restrict__ t, con
     r.t_first = t[r.first];
     r.Lt = t[(end < g.n ? end : g.n) - 1] - (int64_t)kVMax;
     // any order: the span of the first and last timestamps says nothing about the others
-    r.narrow = !g.any_order && (r.Lt + (int64_t)kVMax) - r.t_first < (int64_t)kVMax;
+    r.narrow = !g.any_order && !beyond_double(r.t_first, r.Lt + (int64_t)kVMax) &&
+               (r.Lt + (int64_t)kVMax) - r.t_first < (int64_t)kVMax;
     r.dlt = r.narrow ? (uint32_t)(r.t_first - r.Lt) : 0u;
     return r;
 }
@@ -790,7 +804,8 @@ __device__ __forceinline__ uint32_t win_value(const ArcLds &L, int wp, uint32_t 
     return mk ? L.T[31 - __clz(mk)][wp] : m.bc;
 }
 
-// Exact int64 arc test of one circle around window pixel wp0 (global pixel q0) for slice j:
+// Exact arc test of one circle around window pixel wp0 (global pixel q0) for slice j, on the
+// reference's own ordering of the int64 values (double_key):
 // V = the group value (v' + L, or the timestamp of the stored event index) where a slice <= j of
 // the group touched the pixel, else B_g.  Rare fallback; out of line so its registers do not
 // raise the pressure of the main kernel body.
@@ -802,6 +817,18 @@ struct ExactCtx {
     bool narrow;
 };
 
+// Order key of (double)v: k(a) > k(b) <=> (double)a > (double)b.  The reference's arc scan takes
+// its minimum and its `>=` on (double)t (:977-990, :1024-1036), and a streak passes exactly when
+// every value of the arc is greater IN DOUBLE than every value outside it (which implies the two
+// int64 neighbour comparisons, :968/:972), so arc_streak on these keys is the reference's test.
+// Below 2^53 in magnitude the conversion is exact and the order is the int64 one.  The bits of a
+// non-negative double order as integers; a negative one's magnitude bits are flipped (an int64
+// never converts to -0.0 or NaN).
+__device__ __forceinline__ int64_t double_key(int64_t v) {
+    const int64_t b = __builtin_bit_cast(int64_t, (double)v);
+    return b ^ ((b >> 63) & INT64_MAX);
+}
+
 template <int N>
 __device__ __forceinline__ void exact_values(const ArcLds *L, int wp0, int64_t q0, uint32_t below,
                                              const int8_t *dy, const int8_t *dx, const ExactCtx &c, int64_t (&v)[N]) {
@@ -812,9 +839,9 @@ __device__ __forceinline__ void exact_values(const ArcLds *L, int wp0, int64_t q
         const int wp = wp0 + dy[k] * kWin + dx[k];
         const uint32_t mk = L->mb[wp].mask & below;
         const uint32_t tv = mk ? L->T[31 - __clz(mk)][wp] : 0u;
-        v[k] = !mk      ? c.Bg[q0 + (int64_t)dy[k] * c.W + dx[k]]
-               : c.narrow ? c.Lt + (int64_t)tv
-                          : c.t[c.grp_first + tv - 1u];
+        v[k] = double_key(!mk        ? c.Bg[q0 + (int64_t)dy[k] * c.W + dx[k]]
+                          : c.narrow ? c.Lt + (int64_t)tv
+                                     : c.t[c.grp_first + tv - 1u]);
     }
 }
 

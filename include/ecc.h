@@ -248,6 +248,12 @@ int ecc_kmeans_assign_f32(ecc_ctx *ctx, const float *xy, int64_t n_points, const
  * (x<m || x>=W-m || y<m || y>=H-m, m = margin 4, W/H = sensor size: Q12) are skipped
  * (border_mode 0 = fixed) or end the slice's tests (border_mode 1 = ref_compat `break`,
  * Q11); corner = circle3 streak (len 3..6 of 16) AND circle4 streak (len 4..8 of 20).
+ * Timestamps are any int64.  The reference compares a streak's two end neighbours as int64 but
+ * takes the arc's minimum and scans the rest of the circle in double (:977-990, :1024-1036).
+ * Below 2^53 ticks in magnitude that is an integer test.  From 2^53 upward neighbouring
+ * timestamps round to the same double and the reference's verdict differs from the int64 one;
+ * the library gives the reference's (groups that reach 2^53 take the exact test, which orders
+ * the values as their doubles), at the exact test's speed.
  * Slices with global index < first_detect_slice are not tested (Q15: pass 1 for a fresh
  * stream, 0 when continuing a stream).
  * sae: DEVICE int64[H*W], row-major, holds the initial SAE on entry and the final SAE on
