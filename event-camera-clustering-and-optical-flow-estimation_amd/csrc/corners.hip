@@ -15,6 +15,7 @@
 // Pipeline (every launch covers the whole batch):
 //   bin_hist / scan / bin_scatter: counting sort by (group, 14x14-pixel TILE) into 4-byte keys
 //       (event index within the group << 8 | pixel within the tile) + group-relative timestamps;
+//       the sort also writes each group's constants (GroupRec) for the kernels below;
 //   pair_build: per (group, tile) the distinct (slice, pixel) pairs with the value an arc test
 //               reads there, in sub-region order; the slices that touched each pixel and its
 //               last timestamp;
@@ -32,6 +33,8 @@
 // separated iff its size is s.  This branch-free form is exact; tests/test_gpu_parity.py
 // checks it against the literal loop in oracle/oracle.cpp.
 // Algorithmic bytes: 12 B/event in (xy + t) + 1 B/event out (corner flag).
+#include "arc_select.hpp"
+#include "corner_decode.hpp"
 #include "ecc_internal.hpp"
 
 #include <cstdio>
@@ -66,8 +69,17 @@ struct CornerGeom {
     int tiles_x, n_tiles;  // bin n_tiles of each group holds the events outside the sensor
     int seg_stride;        // words per slice of the slice-major corner pairs: n_tiles * 7, to 16 B
     float inv_S;
+    // item -> (group, tile) and tile -> (row, column) without a runtime division (MagicDiv)
+    uint32_t nt_mul, nt_sh, tx_mul, tx_sh;
     int64_t n, n_slices;
 };
+
+// item = group * n_tiles + tile (n_items < 2^31: host check)
+__device__ __forceinline__ void item_decode(const CornerGeom &g, int64_t item, int64_t &grp, int &tile) {
+    const uint32_t q = magic_quot((uint32_t)item, g.nt_mul, g.nt_sh);
+    grp = q;
+    tile = (int)((uint32_t)item - q * (uint32_t)g.n_tiles);
+}
 
 // Batch sorted per slice by tile: slice s keeps its own range [s*S, s*S + len_s), and tile b of
 // slice s is [s*S + toff[s][b], s*S + toff[s][b+1]) (row length n_tiles + 2: the outside-sensor
@@ -89,17 +101,25 @@ __device__ __forceinline__ bool is_border(int x, int y, const CornerGeom &g) {
 
 __device__ __forceinline__ int tile_of(uint32_t v, const CornerGeom &g) {
     const int x = ecc::xy_x(v), y = ecc::xy_y(v);
-    if (x >= g.W || y >= g.H) return g.n_tiles;
-    return (y / kTile) * g.tiles_x + x / kTile;
+    // a select, not a branch; y / 14 and tiles_x are below 2^13: a 24-bit multiply
+    const int tl = (int)__umul24((uint32_t)(y / kTile), (uint32_t)g.tiles_x) + x / kTile;
+    return (x >= g.W || y >= g.H) ? g.n_tiles : tl;
 }
 
 __device__ __forceinline__ uint32_t tile_key(uint32_t v, uint32_t e_local) {
     return (e_local << 8) | (uint32_t)((ecc::xy_y(v) % kTile) * kTile + ecc::xy_x(v) % kTile);
 }
 
+// tile = ty * tiles_x + tx
+__device__ __forceinline__ void tile_origin_xy(const CornerGeom &g, int tile, int &tx, int &ty) {
+    ty = (int)magic_quot((uint32_t)tile, g.tx_mul, g.tx_sh);
+    tx = tile - ty * g.tiles_x;
+}
 __device__ __forceinline__ void tile_origin(const CornerGeom &g, int tile, int &x0, int &y0) {
-    x0 = (tile % g.tiles_x) * kTile;
-    y0 = (tile / g.tiles_x) * kTile;
+    int tx, ty;
+    tile_origin_xy(g, tile, tx, ty);
+    x0 = tx * kTile;
+    y0 = ty * kTile;
 }
 
 // The reference compares the two streak-end neighbours as int64 but scans the arc in double
@@ -160,7 +180,13 @@ constexpr int kSortEPT = 16;
 #endif
 constexpr int kSortFence = ECC_SORT_FENCE;  // events whose loads may be in flight together
 constexpr int kSortChunk = kSortThreads * kSortEPT;
-constexpr int kSortWaves = kSortThreads / 64;
+// Event slots without an event (past the slice's end, or dropped by the dedup) are data, not a
+// saved exec mask per unrolled slot: they count into kSortSent sentinel bins after the real ones
+// (one per LDS bank, so the lanes of a wave do not pile on one address).  The scan runs over the
+// sentinel bins too, so they start at `kept` and a chunk's 16384 slots fill the staging area
+// exactly: the histogram add and the placement run unpredicated, the sentinel slots landing
+// past the kept keys, where nothing reads them.
+constexpr int kSortSent = 32;
 
 // Per-slice (slice, pixel) dedup of the keys (groups with 4-byte keys, slices in one chunk, time
 // order intact): an arc test reads, per (slice, pixel), only the largest timestamp, i.e. the key
@@ -202,11 +228,16 @@ __device__ __forceinline__ int block_excl_scan_inplace(int32_t *a, int n, int32_
     return total;
 }
 
+struct GroupRec;  // the group's constants (below, with GroupRef)
+__device__ __forceinline__ void group_rec_store(const int64_t *__restrict__ t, const CornerGeom &g, int64_t grp,
+                                                GroupRec *__restrict__ grec);
+
+template <bool kBorder>  // border_mode 1: the slice's first border event is wanted
 __global__ void __launch_bounds__(kSortThreads, 8)  // 8 waves/SIMD: two workgroups per CU
 slice_sort_kernel(const uint32_t *__restrict__ xy, const int64_t *__restrict__ t, CornerGeom g, Sorted so,
                   int32_t *__restrict__ first_border, int32_t *__restrict__ err, int32_t tag,
-                  uint32_t *__restrict__ zero0, int32_t *__restrict__ zero1) {
-    extern __shared__ int32_t hist[];  // [nb]: counts, then offsets, then (long slices) cursors;
+                  uint32_t *__restrict__ zero0, int32_t *__restrict__ zero1, GroupRec *__restrict__ grec) {
+    extern __shared__ int32_t hist[];  // [nb + kSortSent]: counts, then offsets, then (long slices) cursors;
                                        // then [kSortChunk] staging (single slices: the keys in
                                        // event order, then in tile order); then the dedup bitmap
     __shared__ int32_t wsum[kSortThreads / 64];
@@ -223,15 +254,19 @@ slice_sort_kernel(const uint32_t *__restrict__ xy, const int64_t *__restrict__ t
     const int len = (int)((lo + g.S < g.n ? lo + g.S : g.n) - lo);
     const int64_t grp = s / kGroup;
     const int64_t grp_first = grp * kGroup * (int64_t)g.S;
+    // the group's record for the later kernels of the call (rewritten by every sort phase)
+    if (s % kGroup == 0 && tid == 0) group_rec_store(t, g, grp, grec);
     int64_t t_first;
     const bool narrow = group_narrow(t, g, grp, &t_first);  // uniform
     const bool fmt4 = group_fmt4(t, g, grp);                // uniform
     const int nb = g.n_tiles + 1;
     const bool single = len <= kSortChunk;
     const bool dedup = ECC_SORT_DEDUP && single && fmt4 && g.dedup_words > 0;  // uniform
-    uint32_t *stage = reinterpret_cast<uint32_t *>(hist + nb);
+    const int nbs = nb + kSortSent;
+    const uint32_t sent = (uint32_t)(nb + (lane & (kSortSent - 1))) << 16;  // this lane's sentinel bin
+    uint32_t *stage = reinterpret_cast<uint32_t *>(hist + nbs);
     uint32_t *bm = stage + kSortChunk;  // the dedup bitmap
-    for (int b = tid; b < nb; b += kSortThreads) hist[b] = 0;
+    for (int b = tid; b < nbs; b += kSortThreads) hist[b] = 0;
     if (dedup)
         for (int w = tid; w < g.dedup_words; w += kSortThreads) bm[w] = 0u;
     __syncthreads();
@@ -254,12 +289,14 @@ slice_sort_kernel(const uint32_t *__restrict__ xy, const int64_t *__restrict__ t
             const int ic = ok ? i : len - 1;  // clamped: unconditional loads off uniform bases
             const uint32_t v = xs[ic];
             const int64_t tc = ts[ic];
-            // the previous event's t: a coalesced load of the neighbouring element (cache hit)
+            // the previous event's t: a coalesced load of the neighbouring element (cache hit).  A
+            // clamped slot repeats the check of the slice's last event, so the verdict needs no
+            // `ok`: no per-slot mask pair is kept alive.
             const int64_t tp = (ic > 0 || lo > 0) ? ts[ic - 1] : INT64_MIN;
-            bad |= ok && tp > tc;
+            bad |= tp > tc;
             if (single) stage[u * kSortThreads + tid] = tile_key(v, fmt4 ? (uint32_t)(tc - t_first) : (uint32_t)(lo + i - grp_first));
-            br[u] = ok ? (uint32_t)tile_of(v, g) << 16 : 0xffffffffu;
-            if (ok && is_border(ecc::xy_x(v), ecc::xy_y(v), g)) fb = min(fb, i);
+            br[u] = ok ? (uint32_t)tile_of(v, g) << 16 : sent;
+            if (kBorder && ok && is_border(ecc::xy_x(v), ecc::xy_y(v), g)) fb = min(fb, i);
         }
         if (dedup && !__syncthreads_or(bad)) {  // uniform (single slices: one pass of this loop)
             // rounds of kSortDedupStep event slots, latest first: an event is dropped when a later
@@ -273,7 +310,7 @@ slice_sort_kernel(const uint32_t *__restrict__ xy, const int64_t *__restrict__ t
 #pragma unroll
                 for (int d = 0; d < kSortDedupStep; ++d) {
                     const int u = u0 - d;
-                    const uint32_t b = br[u] >> 16;  // 0xffff: no event; n_tiles: outside the sensor (kept)
+                    const uint32_t b = br[u] >> 16;  // > n_tiles: no event; n_tiles: outside the sensor (kept)
                     cand[d] = b < (uint32_t)g.n_tiles;
                     tp[d] = b * kTilePix + (stage[u * kSortThreads + tid] & 255u);  // own key
                     drop[d] = u0 < kSortEPT - 1 && cand[d] && ((bm[tp[d] >> 5] >> (tp[d] & 31u)) & 1u);
@@ -281,30 +318,30 @@ slice_sort_kernel(const uint32_t *__restrict__ xy, const int64_t *__restrict__ t
                 if (u0 < kSortEPT - 1) __syncthreads();  // every check of the round before its bits are set
 #pragma unroll
                 for (int d = 0; d < kSortDedupStep; ++d) {
-                    if (drop[d]) br[u0 - d] = 0xffffffffu;
+                    if (drop[d]) br[u0 - d] = sent;
                     else if (cand[d]) atomicOr(&bm[tp[d] >> 5], 1u << (tp[d] & 31u));
                 }
                 if (u0 - kSortDedupStep >= 0) __syncthreads();  // the round's bits before the next checks
             }
         }
 #pragma unroll
-        for (int u = 0; u < kSortEPT; ++u) {
-            if (br[u] == 0xffffffffu) continue;
-            br[u] |= (uint32_t)atomicAdd(&hist[br[u] >> 16], 1) & 0xffffu;
-        }
+        for (int u = 0; u < kSortEPT; ++u) br[u] |= (uint32_t)atomicAdd(&hist[br[u] >> 16], 1) & 0xffffu;
     }
     if (__any(bad) && lane == 0 && !g.any_order) *err = tag;  // pending: published by sae_prefix_kernel
-    fb = ecc::wave_min_i32(fb);  // DPP
-    if (lane == 0) wsum[tid >> 6] = fb;
-    __syncthreads();
-    if (tid == 0) {
-        int m = 0x7fffffff;
-        for (int w = 0; w < kSortThreads / 64; ++w) m = min(m, wsum[w]);
-        first_border[s] = m;
+    if (kBorder) {  // (border_mode 0: the flag pass does not read first_border)
+        fb = ecc::wave_min_i32(fb);  // DPP
+        if (lane == 0) wsum[tid >> 6] = fb;
+        __syncthreads();
+        if (tid == 0) {
+            int m = 0x7fffffff;
+            for (int w = 0; w < kSortThreads / 64; ++w) m = min(m, wsum[w]);
+            first_border[s] = m;
+        }
     }
     __syncthreads();
-    const int kept = block_excl_scan_inplace(hist, nb, wsum);  // len, less the dropped events
+    block_excl_scan_inplace(hist, nbs, wsum);
     __syncthreads();
+    const int kept = hist[nb];  // the first sentinel bin's offset: len, less the dropped events
     int32_t *row = so.toff + s * (int64_t)(nb + 1);
     for (int b = tid; b < nb; b += kSortThreads) row[b] = hist[b];
     if (tid == 0) row[nb] = kept;
@@ -314,15 +351,14 @@ slice_sort_kernel(const uint32_t *__restrict__ xy, const int64_t *__restrict__ t
         for (int u = 0; u < kSortEPT; ++u) kv[u] = stage[u * kSortThreads + tid];  // own keys
         __syncthreads();  // every key read before the stage is permuted
 #pragma unroll
-        for (int u = 0; u < kSortEPT; ++u)
-            if (br[u] != 0xffffffffu) stage[hist[br[u] >> 16] + (br[u] & 0xffffu)] = kv[u];
+        for (int u = 0; u < kSortEPT; ++u) stage[hist[br[u] >> 16] + (br[u] & 0xffffu)] = kv[u];
         __syncthreads();
         for (int i = tid; i < kept; i += kSortThreads) so.key[lo + i] = stage[i];
         if (fmt4 || !narrow) return;  // (no dedup below: kept == len)
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < kSortEPT; ++u)  // rare (groups spanning >= 2^24 ticks): t read again
-            if (br[u] != 0xffffffffu) stage[hist[br[u] >> 16] + (br[u] & 0xffffu)] = (uint32_t)(t[lo + u * kSortThreads + tid] - t_first);
+        for (int u = 0; u < kSortEPT; ++u)  // rare (groups spanning >= 2^24 ticks): t read again (clamped)
+            stage[hist[br[u] >> 16] + (br[u] & 0xffffu)] = (uint32_t)(t[lo + min(u * kSortThreads + tid, len - 1)] - t_first);
         __syncthreads();
         for (int i = tid; i < len; i += kSortThreads) so.t32[lo + i] = stage[i];
         return;
@@ -407,6 +443,49 @@ __device__ __forceinline__ GroupRef group_ref(const int64_t *__restrict__ t, con
     return r;
 }
 
+// The group's constants, written once per call by slice_sort's workgroup of the group's first
+// slice (which holds every input) and read by pair_build and the arc kernels with one scalar
+// load (each of their waves used to rebuild them from two dependent loads of t).  slice_sort
+// itself computes its own verdicts: its other workgroups may run before the writer.
+struct GroupRec {
+    int64_t first, t_first, Lt;
+    uint32_t dlt;
+    uint32_t bits;  // kRecNarrow: GroupRef::narrow; kRecFmt4: group_fmt4.  kRecNarrow32 (group_narrow)
+                    // and kRecBeyond (beyond_double) complete the record but have no reader yet:
+                    // only slice_sort needs them, and it computes its own (one thread per group pays)
+};
+static_assert(sizeof(GroupRec) == 32, "one 32-B scalar load");
+constexpr uint32_t kRecNarrow = 1u, kRecFmt4 = 2u, kRecNarrow32 = 4u, kRecBeyond = 8u;
+
+__device__ __forceinline__ GroupRec group_rec_make(const int64_t *__restrict__ t, const CornerGeom &g, int64_t grp) {
+    const GroupRef r = group_ref(t, g, grp);
+    int64_t t_first;
+    GroupRec rec;
+    rec.first = r.first;
+    rec.t_first = r.t_first;
+    rec.Lt = r.Lt;
+    rec.dlt = r.dlt;
+    rec.bits = (r.narrow ? kRecNarrow : 0u) | (group_fmt4(t, g, grp) ? kRecFmt4 : 0u) |
+               (group_narrow(t, g, grp, &t_first) ? kRecNarrow32 : 0u) |
+               (beyond_double(r.t_first, r.Lt + (int64_t)kVMax) ? kRecBeyond : 0u);
+    return rec;
+}
+
+__device__ __forceinline__ void group_rec_store(const int64_t *__restrict__ t, const CornerGeom &g, int64_t grp,
+                                                GroupRec *__restrict__ grec) {
+    grec[grp] = group_rec_make(t, g, grp);
+}
+
+__device__ __forceinline__ GroupRef group_ref_of(const GroupRec &rec) {
+    GroupRef r;
+    r.first = rec.first;
+    r.t_first = rec.t_first;
+    r.Lt = rec.Lt;
+    r.narrow = (rec.bits & kRecNarrow) != 0u;
+    r.dlt = rec.dlt;
+    return r;
+}
+
 static_assert(kWin == kTile + 2 * kHalo, "window = tile + halo on both sides");
 static_assert(kHalo >= 4, "the circles reach 4 px from the pixel under test");
 
@@ -427,15 +506,18 @@ constexpr int kRecVals = 4;  // values a pixel record holds inline
 
 __global__ void __launch_bounds__(kThreads)
 pair_build_kernel(const int64_t *__restrict__ t, CornerGeom g, Sorted so, uint32_t *__restrict__ ovf,
-                  uint4 *__restrict__ pv, uint32_t *__restrict__ gmask, int64_t *__restrict__ glast) {
+                  uint4 *__restrict__ pv, uint32_t *__restrict__ gmask, int64_t *__restrict__ glast,
+                  const GroupRec *__restrict__ grec) {
     __shared__ uint32_t tab[kGroup][kTilePix];  // 24.5 KiB
     __shared__ uint32_t pmask[kTilePix];        // slices that touched each tile pixel
     __shared__ int32_t wtot[kThreads / 64];
     __shared__ TileSegs segs;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t item = blockIdx.x;
-    const int64_t grp = (int)item / g.n_tiles;  // n_items < 2^31 (host check): 32-bit division
-    const int tile = (int)item % g.n_tiles;
+    int64_t grp;
+    int tile;
+    item_decode(g, item, grp, tile);
+    const GroupRec rec = grec[grp];  // uniform: one scalar load
     const int lp = tid < kTilePix ? tid : 0;  // this lane's tile pixel
     {
         uint4 *z = reinterpret_cast<uint4 *>(&tab[0][0]);
@@ -443,8 +525,8 @@ pair_build_kernel(const int64_t *__restrict__ t, CornerGeom g, Sorted so, uint32
         if (tid < kTilePix) pmask[tid] = 0u;
     }
     tile_segs(g, so, grp, tile, segs);
-    const GroupRef gr = group_ref(t, g, grp);
-    const bool fmt4 = group_fmt4(t, g, grp);  // uniform; the same test as slice_sort's
+    const GroupRef gr = group_ref_of(rec);
+    const bool fmt4 = (rec.bits & kRecFmt4) != 0u;  // uniform; the same test as slice_sort's
     __syncthreads();
     const int total = segs.pref[kGroup];
     if (fmt4) {  // 4-byte keys: slice = the segment, value = relative t + dlt
@@ -609,89 +691,8 @@ sae_local_last_kernel(CornerGeom g, int64_t n_groups, const uint32_t *__restrict
     }
 }
 
-__device__ __forceinline__ void tile_origin_xy(const CornerGeom &g, int tile, int &tx, int &ty) {
-    tx = tile % g.tiles_x;
-    ty = tile / g.tiles_x;
-}
-
-template <int N, int SMIN, int SMAX>
-__device__ __forceinline__ bool arc_streak(const int64_t (&v)[N]) {
-    int cnt[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) cnt[j] = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-#pragma unroll
-        for (int k = j + 1; k < N; ++k) {
-            cnt[j] += (v[k] > v[j]) ? 1 : 0;
-            cnt[k] += (v[j] > v[k]) ? 1 : 0;
-        }
-    }
-    constexpr uint32_t full = (N == 32) ? 0xffffffffu : ((1u << N) - 1u);
-    bool ok = false;
-#pragma unroll
-    for (int s = SMIN; s <= SMAX; ++s) {
-        uint32_t m = 0;
-#pragma unroll
-        for (int j = 0; j < N; ++j) m |= (cnt[j] < s ? 1u : 0u) << j;
-        const uint32_t rot = ((m << 1) | (m >> (N - 1))) & full;  // bit j <- bit j-1
-        const uint32_t starts = m & ~rot;
-        ok |= (__popc(m) == s) && (__popc(starts) == 1);
-    }
-    return ok;
-}
-
-// ---- fast arc test on 32-bit keys ------------------------------------------------------------
-// Values are mapped to v' = clamp(v - L, 0, 2^27 - 1) with L = t_last(group) - (2^27 - 1) and
-// keyed as (v' << IB) | position.  Clamping merges the values <= L into ties at 0.  This cannot
-// change the outcome when at least SMAX+1 values are unclamped: a witness k (the largest value
-// outside the arc) has <= SMAX values above it, so it and its arc are unclamped and compare as
-// before, while a clamped k' has every unclamped value (> SMAX of them) above it in both
-// forms.  Otherwise (or when some value exceeds t_last) the exact int64 test runs.
-// Batcher odd-even merge sort, descending; with compile-time padding and only the top outputs
-// used, dead compare-exchanges fold away.
-template <int N>
-__device__ __forceinline__ void sort_desc(uint32_t (&k)[N]) {
-#pragma unroll
-    for (int p = 1; p < N; p += p) {
-#pragma unroll
-        for (int kk = p; kk > 0; kk /= 2) {
-#pragma unroll
-            for (int j = kk % p; j + kk < N; j += kk + kk) {
-#pragma unroll
-                for (int i = 0; i < kk; ++i) {
-                    if (i + j + kk < N && (i + j) / (p + p) == (i + j + kk) / (p + p)) {
-                        const uint32_t a = k[i + j], b = k[i + j + kk];
-                        k[i + j] = a > b ? a : b;
-                        k[i + j + kk] = a > b ? b : a;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// 1 = arc found, 0 = none, -1 = undecidable on clamped keys (fewer than SMAX+1 unclamped and
-// the clamped values not all equal).
-template <int N, int NP, int IB, int SMIN, int SMAX>
-__device__ __forceinline__ int arc_keys(uint32_t (&k)[NP], bool ties_exact) {
-    sort_desc<NP>(k);
-    if (!ties_exact && (k[SMAX] >> IB) == 0u) return -1;
-    constexpr uint32_t full = (1u << N) - 1u;
-    uint32_t m = 0;
-    bool ok = false;
-#pragma unroll
-    for (int s = 1; s <= SMAX; ++s) {
-        m |= 1u << (k[s - 1] & ((1u << IB) - 1u));  // IB = 5: the shift's own 5-bit mask, no AND
-        if (s >= SMIN) {
-            // (a >> IB) > (b >> IB)  <=>  a > (b | low IB bits): one OR, one compare
-            const bool sep = k[s - 1] > (k[s] | ((1u << IB) - 1u));
-            const uint32_t rot = ((m << 1) | (m >> (N - 1))) & full;
-            ok |= sep && (__popc(m & ~rot) == 1);
-        }
-    }
-    return ok ? 1 : 0;
-}
+// arc_streak (the count form, used by the exact tests), sort_desc, the selection networks and
+// arc_keys (the fast test on clamped 32-bit keys) are in arc_select.hpp, which the host compiles too.
 
 // Staged neighbourhood of one (group, tile) item.  T[j][wp] holds the value set at window pixel
 // wp by slice j of the group — v' = t - L (narrow groups, exact) or the event index + 1 (wide
@@ -872,8 +873,10 @@ __device__ __noinline__ bool exact_pair_test(const ArcLds *L, int wp0, int64_t q
 
 // The slices of group grp whose pairs are tested (Q15: slices before first_detect are not).
 __device__ __forceinline__ uint32_t eligible_slices(const CornerGeom &g, int64_t grp) {
-    const int64_t j0 = (int64_t)g.first_detect - grp * kGroup;
-    return j0 <= 0 ? 0xffffffffu : (j0 >= kGroup ? 0u : (0xffffffffu << (int)j0));
+    const int gs = (int)grp * kGroup;  // the group's first slice (n_slices < 2^31: host check)
+    if (g.first_detect <= gs) return 0xffffffffu;
+    const int j0 = g.first_detect - gs;  // > 0 with gs >= 0: no overflow
+    return j0 >= kGroup ? 0u : (0xffffffffu << j0);
 }
 
 // The values v3 .. v_{p-1} (p > 4) of a pixel whose record is r, from the overflow array:
@@ -923,10 +926,11 @@ template <int NT>
 __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const int64_t *__restrict__ t, const CornerGeom &g,
                                                const uint32_t *__restrict__ ovf, const uint4 *__restrict__ pv,
                                                const int64_t *__restrict__ gB, const uint32_t *__restrict__ gmask,
-                                               uint32_t *__restrict__ res) {
-    const int64_t grp = (int)item / g.n_tiles;  // n_items < 2^31 (host check): 32-bit division
-    const int tile = (int)item % g.n_tiles;
-    if ((grp + 1) * kGroup <= g.first_detect) return;  // every slice of the group precedes detection
+                                               uint32_t *__restrict__ res, const GroupRec *__restrict__ grec) {
+    int64_t grp;
+    int tile;
+    item_decode(g, item, grp, tile);
+    if ((int)grp < (g.first_detect >> 5)) return;  // (grp + 1) * 32 <= first_detect: every slice precedes detection
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #if ECC_ARC_PROFILE
     const unsigned long long dense_t0_ = wall_clock64();
@@ -936,7 +940,7 @@ __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const in
     int tx, ty;
     tile_origin_xy(g, tile, tx, ty);
     const int x0 = tx * kTile, y0 = ty * kTile;
-    const GroupRef gr = group_ref(t, g, grp);
+    const GroupRef gr = group_ref_of(grec[grp]);  // uniform: one scalar load
     const int64_t grp_first = gr.first, Lt = gr.Lt;
     const bool narrow = gr.narrow;
     const int64_t *Bg = gB + grp * HW;
@@ -1039,7 +1043,7 @@ __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const in
             uint32_t k3[16];
 #pragma unroll
             for (int k = 0; k < 16; ++k) k3[k] = (win_value(L, wp0 + c3dy[k] * kWin + c3dx[k], below) << 5) | k;
-            const int r3 = arc_keys<16, 16, 5, 3, 6>(k3, ties_exact);
+            const int r3 = arc_keys<16, 5, 3, 6>(k3, ties_exact);
             if (r3 > 0) {
                 const int qi = atomicAdd(&L.q4n, 1);
                 if (qi < kQ4Cap) L.q4[qi] = (uint16_t)ti;
@@ -1058,12 +1062,10 @@ __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const in
         const int pi = L.tasks[ti];
         const int j = pi >> 9, wp0 = pi & 511;
         const uint32_t below = below_mask(j);
-        uint32_t k4[32];
+        uint32_t k4[20];
 #pragma unroll
         for (int k = 0; k < 20; ++k) k4[k] = (win_value(L, wp0 + c4dy[k] * kWin + c4dx[k], below) << 5) | k;
-#pragma unroll
-        for (int k = 20; k < 32; ++k) k4[k] = 0u;
-        const int r4 = arc_keys<20, 32, 5, 4, 8>(k4, ties_exact);
+        const int r4 = arc_keys<20, 5, 4, 8>(k4, ties_exact);
         if (r4 > 0) {  // the pair's bit: slice j, tile pixel (wp0's row and column less the halo)
             const int rb = j * kTilePix + (wp0 / kWin - kHalo) * kTile + (wp0 % kWin - kHalo);
             atomicOr(&L.res[rb >> 5], 1u << (rb & 31));
@@ -1124,8 +1126,7 @@ struct SparseLds {
     uint16_t q4[kQ4Cap];
     int64_t wave_c0[kWaves];    // the wave's first B_g at or below L (clamped to 0) ...
     int32_t wave_cf[kWaves];    // ... bit 1: it has one, bit 0: another differs from it
-    int32_t wave_tot[kWaves];
-    int32_t wave_own[kWaves];  // the wave's own-tile pixels have pairs
+    int32_t wave_tot[kWaves];   // the wave's counts and its own-tile flag, packed (arc_item)
     int32_t exact_only, mixed, q4n, redo;
 };
 
@@ -1177,9 +1178,10 @@ __device__ __forceinline__ void arc_prefetch(ArcPre &p, int64_t item, const Corn
     p.mk = 0u;
     p.rec = make_uint4(0u, 0u, 0u, 0u);
     const int64_t HW = (int64_t)g.H * g.W;
-    const int64_t grp = (int)item / g.n_tiles;  // n_items < 2^31 (host check): 32-bit division
-    const int tile = (int)item % g.n_tiles;
-    const int tx = tile % g.tiles_x, ty = tile / g.tiles_x;
+    int64_t grp;
+    int tile, tx, ty;
+    item_decode(g, item, grp, tile);
+    tile_origin_xy(g, tile, tx, ty);
     const int wx = tx * kTile - kHalo + tid % kWin, wy = ty * kTile - kHalo + tid / kWin;
     if (tid < kWinPix && wx >= 0 && wy >= 0 && wx < g.W && wy < g.H) {
         const int64_t q = grp * HW + (int64_t)wy * g.W + wx;
@@ -1197,22 +1199,25 @@ __device__ __forceinline__ void arc_prefetch(ArcPre &p, int64_t item, const Corn
 // minimum of B_g are all wave scans before the first barrier, and each lane writes its pixel's
 // list and tasks itself (no scatter, no LDS atomics).
 __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPre &pre,
-                                         const int64_t *__restrict__ t, const CornerGeom &g,
+                                         const GroupRec *__restrict__ grec, const CornerGeom &g,
                                          const uint32_t *__restrict__ ovf, uint32_t *__restrict__ res,
                                          int64_t *__restrict__ over, uint32_t *__restrict__ n_over) {
-    const int64_t grp = (int)item / g.n_tiles;  // n_items < 2^31 (host check): 32-bit division
-    const int tile = (int)item % g.n_tiles;
-    if ((grp + 1) * kGroup <= g.first_detect) return;  // every slice of the group precedes detection
+    int64_t grp;
+    int tile;
+    item_decode(g, item, grp, tile);
+    if ((int)grp < (g.first_detect >> 5)) return;  // (grp + 1) * 32 <= first_detect: every slice precedes detection
+    static_assert(kGroup == 32, "first_detect >> 5");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);  // in a scalar register: uniform selects
 #if ECC_ARC_PROFILE
     unsigned long long arc_t_ = wall_clock64(), arc_ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     int tx, ty;
     tile_origin_xy(g, tile, tx, ty);
     const int x0 = tx * kTile, y0 = ty * kTile;
-    const GroupRef gr = group_ref(t, g, grp);
-    const int64_t Lt = gr.Lt;
-    const bool narrow = gr.narrow;
+    const GroupRec rec = grec[grp];  // uniform: one scalar load
+    const int64_t Lt = rec.Lt;
+    const bool narrow = (rec.bits & kRecNarrow) != 0u;
     const int wp = tid;
     const bool win_lane = wp < kWinPix;
     const int64_t bq = pre.bq;
@@ -1230,10 +1235,14 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
     const int cnt = win_lane ? __popc(mk_w) + 1 : 0;  // the pixel's values + its B_g slot
     const int tcnt = __popc(tm);
     // wave scans and the wave minimum of B_g by DPP moves
-    // one scan of both counts, packed (task count << 16 | value count: a workgroup's sums stay
-    // below 2^16, at most 484 * 33 values and 196 * 32 tasks)
-    const int both = ecc::wave_incl_scan(tcnt << 16 | cnt);
-    const int incl = both & 0xffff, tincl = both >> 16;
+    // one scan of both counts, packed (task count << kTaskShift | value count: a workgroup's sums
+    // are at most 484 * 33 < 2^14 values and 196 * 32 < 2^13 tasks); the wave's word for the
+    // others adds its "own-tile pixels have pairs" flag above them (eight of them sum below 2^4),
+    // so the packed words are summed as they are and unpacked once
+    constexpr int kTaskShift = 14, kOwnShift = 27;
+    constexpr int kCntMask = (1 << kTaskShift) - 1, kTaskMask = (1 << (kOwnShift - kTaskShift)) - 1;
+    const int both = ecc::wave_incl_scan(tcnt << kTaskShift | cnt);
+    const int incl = both & kCntMask, tincl = both >> kTaskShift;
     const uint64_t own_pairs = __ballot(own && mk_w != 0u);
     int64_t c0;
     int cf;
@@ -1256,24 +1265,24 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
 #pragma unroll
         for (int u = 0; u < kXpf; ++u) xs[u] = x4[min(u, nl - 1)];  // no load past the run
     }
-    if (lane == 63) L.wave_tot[wave] = both;
+    if (lane == 63) L.wave_tot[wave] = both | (own_pairs != 0ull ? 1 << kOwnShift : 0);
     if (lane == 0) {
         L.wave_c0[wave] = c0;
         L.wave_cf[wave] = cf;
-        L.wave_own[wave] = own_pairs != 0ull;
     }
     __syncthreads();  // 1
     ARC_MARK(0);  // A
-    int total = 0, n_tasks = 0, any_own = 0, off = incl - cnt, toff = tincl - tcnt;
+    int sum = 0, before = 0;  // packed: all waves, the waves ahead of this one
 #pragma unroll
     for (int w = 0; w < kWaves; ++w) {  // uniform reads, in flight together
-        const int wb = L.wave_tot[w], wt = wb & 0xffff, tt = wb >> 16;
-        total += wt;
-        n_tasks += tt;
-        off += w < wave ? wt : 0;
-        toff += w < wave ? tt : 0;
-        any_own |= L.wave_own[w];
+        const int wb = L.wave_tot[w];
+        sum += wb;
+        before += w < wave_s ? wb : 0;
     }
+    const int total = sum & kCntMask, any_own = sum >> kOwnShift;
+    int n_tasks = (sum >> kTaskShift) & kTaskMask;
+    const int off = incl - cnt + (before & kCntMask);
+    int toff = tincl - tcnt + ((before >> kTaskShift) & kTaskMask);
     if (wave == 0) {  // L.mixed is read after barrier 2
         const bool mixed = clamp_mixed<kWaves>(L.wave_c0, L.wave_cf, lane);
         if (lane == 0) L.mixed = mixed;
@@ -1335,7 +1344,7 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
         uint32_t k3[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) k3[k] = (sparse_value(L, wp0 + c3dy[k] * kWin + c3dx[k], below) << 5) | k;
-        const int r3 = arc_keys<16, 16, 5, 3, 6>(k3, ties_exact);
+        const int r3 = arc_keys<16, 5, 3, 6>(k3, ties_exact);
         if (r3 > 0) {
             const int qi = atomicAdd(&L.q4n, 1);
             if (qi < kQ4Cap) L.q4[qi] = (uint16_t)pi;
@@ -1361,12 +1370,10 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
         const int pt = L.q4[qi];  // j << 9 | window pixel
         const int j = pt >> 9, wp0 = pt & 511;
         const uint32_t below = below_mask(j);
-        uint32_t k4[32];
+        uint32_t k4[20];
 #pragma unroll
         for (int k = 0; k < 20; ++k) k4[k] = (sparse_value(L, wp0 + c4dy[k] * kWin + c4dx[k], below) << 5) | k;
-#pragma unroll
-        for (int k = 20; k < 32; ++k) k4[k] = 0u;
-        const int r4 = arc_keys<20, 32, 5, 4, 8>(k4, ties_exact);
+        const int r4 = arc_keys<20, 5, 4, 8>(k4, ties_exact);
         if (r4 > 0) {  // the pair's bit: slice j, tile pixel (wp0's row and column less the halo)
             const int pi = j * kTilePix + (wp0 / kWin - kHalo) * kTile + (wp0 % kWin - kHalo);
             atomicOr(&L.res[pi >> 5], 1u << (pi & 31));
@@ -1393,7 +1400,7 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
 // runs on XCD b % 8, so XCD x takes the contiguous item range [x * per, (x + 1) * per) —
 // neighbouring tiles of one group share that XCD's L2.
 __global__ void __launch_bounds__(kArcThreads, ECC_ARC_WAVES)  // waves/SIMD: 8 = four 8-wave workgroups per CU
-arc_kernel(const int64_t *__restrict__ t, CornerGeom g, int64_t n_items, const uint32_t *__restrict__ ovf,
+arc_kernel(const GroupRec *__restrict__ grec, CornerGeom g, int64_t n_items, const uint32_t *__restrict__ ovf,
            const uint4 *__restrict__ pv, const int64_t *__restrict__ gB, const uint32_t *__restrict__ gmask,
            uint32_t *__restrict__ res, int64_t *__restrict__ over, uint32_t *__restrict__ n_over) {
     __shared__ SparseLds L;
@@ -1402,7 +1409,7 @@ arc_kernel(const int64_t *__restrict__ t, CornerGeom g, int64_t n_items, const u
     if (item >= n_items) return;
     ArcPre pre;
     arc_prefetch(pre, item, g, pv, gB, gmask);
-    arc_item(L, item, pre, t, g, ovf, res, over, n_over);
+    arc_item(L, item, pre, grec, g, ovf, res, over, n_over);
 }
 
 
@@ -1415,11 +1422,12 @@ constexpr int kDenseThreads = ECC_DENSE_THREADS;
 __global__ void __launch_bounds__(kDenseThreads, 4)  // 4 waves/SIMD (128 VGPRs)
 arc_dense_kernel(const int64_t *__restrict__ t, CornerGeom g, const int64_t *__restrict__ over,
                  const uint32_t *__restrict__ n_over, const uint32_t *__restrict__ ovf, const uint4 *__restrict__ pv,
-                 const int64_t *__restrict__ gB, const uint32_t *__restrict__ gmask, uint32_t *__restrict__ res) {
+                 const int64_t *__restrict__ gB, const uint32_t *__restrict__ gmask, uint32_t *__restrict__ res,
+                 const GroupRec *__restrict__ grec) {
     __shared__ ArcLds L;
     const uint32_t n = *n_over;
     for (uint32_t li = blockIdx.x; li < n; li += gridDim.x) {
-        arc_dense_item<kDenseThreads>(L, over[li], t, g, ovf, pv, gB, gmask, res);
+        arc_dense_item<kDenseThreads>(L, over[li], t, g, ovf, pv, gB, gmask, res, grec);
         __syncthreads();
     }
 }
@@ -1649,6 +1657,7 @@ struct GroupImages {
     uint32_t *ovf;        // [n] the values past a record's first three, in each item's part of the range
     int64_t *over;        // [n_items] items arc_kernel leaves to arc_dense_kernel (heavy or undecidable)
     uint32_t *n_over;     // [0]: their count
+    GroupRec *grec;       // [n_groups] the groups' constants (slice_sort writes, the later kernels read)
 };
 
 Sorted carve_sorted(Carve &cv, const CornerGeom &g, int64_t n_items, int64_t n_groups, int32_t **first_border,
@@ -1666,6 +1675,7 @@ Sorted carve_sorted(Carve &cv, const CornerGeom &g, int64_t n_items, int64_t n_g
     gi->ovf = cv.take<uint32_t>((size_t)g.n + 4 * (size_t)n_items + 8);
     gi->over = cv.take<int64_t>((size_t)n_items);
     gi->n_over = cv.take<uint32_t>(64);
+    gi->grec = cv.take<GroupRec>((size_t)n_groups);
     return so;
 }
 
@@ -1750,11 +1760,15 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
     g.tiles_x = (g.W + kTile - 1) / kTile;
     g.n_tiles = g.tiles_x * ((g.H + kTile - 1) / kTile);
     g.seg_stride = (g.n_tiles * kSegWords + 3) & ~3;
+    {
+        const MagicDiv nt = magic_div31((uint32_t)g.n_tiles), tx = magic_div31((uint32_t)g.tiles_x);
+        g.nt_mul = nt.mul, g.nt_sh = nt.sh, g.tx_mul = tx.mul, g.tx_sh = tx.sh;
+    }
     if (g.n_tiles > kMaxTiles) return ECC_ERR_INVALID;  // > 8191 16x16 tiles (~2.1 Mpixel)
     // slice_sort's dedup bitmap (one bit per tile pixel), kept only while two of its workgroups
     // still fit a CU's LDS (sensors up to ~400 tiles of 14x14 pixels, e.g. 346x260)
     g.dedup_words = (int)(((int64_t)g.n_tiles * kTilePix + 31) / 32);
-    if (((size_t)g.n_tiles + 1 + kSortChunk + g.dedup_words) * 4 + 256 > 80 * 1024) g.dedup_words = 0;
+    if (((size_t)g.n_tiles + 1 + kSortSent + kSortChunk + g.dedup_words) * 4 + 256 > 80 * 1024) g.dedup_words = 0;
     g.n = n;
     g.n_slices = (n + g.S - 1) / g.S;
     if (g.n_slices > INT32_MAX) return ECC_ERR_INVALID;
@@ -1788,24 +1802,26 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
     if (phases & 1) {
     {
         // > 64 KiB: opt in (gfx950 has 160 KiB); the dedup bitmap only while two workgroups fit a CU
-        const size_t lds = ((size_t)nb + kSortChunk + g.dedup_words) * 4;
-        static int lds_set = 0;
-        if ((int)lds > lds_set) {
-            ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&slice_sort_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)((size_t)kMaxTiles * 4 + 4 + kSortChunk * 4)),
+        const size_t lds = ((size_t)nb + kSortSent + kSortChunk + g.dedup_words) * 4;
+        constexpr int kLdsCap = (kMaxTiles + 1 + kSortSent + kSortChunk) * 4;
+        static int lds_set[2] = {0, 0};
+        const int bm = g.border_mode == 1 ? 1 : 0;
+        const auto kern = bm ? &slice_sort_kernel<true> : &slice_sort_kernel<false>;
+        if ((int)lds > lds_set[bm]) {
+            ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap),
                           "slice_sort LDS");
-            lds_set = kMaxTiles * 4 + 4 + kSortChunk * 4;
+            lds_set[bm] = kLdsCap;
         }
         ECC_TIMED(ctx, s, "slice_sort_kernel");
-        hipLaunchKernelGGL(slice_sort_kernel, dim3((unsigned)g.n_slices), dim3(kSortThreads), lds, s, xy, t, g,
+        hipLaunchKernelGGL(kern, dim3((unsigned)g.n_slices), dim3(kSortThreads), lds, s, xy, t, g,
                            so, first_border, ctx->flags + kSortPendingWord, st->prep_tag,
-                           (phases & 2) ? gi.n_over : nullptr, zero_nms_err);
+                           (phases & 2) ? gi.n_over : nullptr, zero_nms_err, gi.grec);
     }
     {
         ECC_TIMED(ctx, s, "pair_build_kernel");
         hipLaunchKernelGGL(pair_build_kernel, dim3((unsigned)n_items), dim3(kThreads), 0, s, t, g, so, gi.ovf, gi.pv,
-                           gi.mask, gi.B);
+                           gi.mask, gi.B, (const GroupRec *)gi.grec);
     }
     if (local_last) {
         ECC_TIMED(ctx, s, "sae_local_last_kernel");
@@ -1837,7 +1853,7 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
         ECC_TIMED(ctx, s, "arc_kernel");
         {
             const unsigned grid = (unsigned)(8 * ((n_items + 7) / 8));  // multiple of 8 (XCD-aware order)
-            hipLaunchKernelGGL(arc_kernel, dim3(grid), dim3(kArcThreads), 0, s, t, g, n_items,
+            hipLaunchKernelGGL(arc_kernel, dim3(grid), dim3(kArcThreads), 0, s, (const GroupRec *)gi.grec, g, n_items,
                                (const uint32_t *)gi.ovf, (const uint4 *)gi.pv, (const int64_t *)gi.B, (const uint32_t *)gi.mask, gi.res, gi.over, gi.n_over);
         }
     }
@@ -1845,7 +1861,7 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
         ECC_TIMED(ctx, s, "arc_dense_kernel");  // the items arc_kernel left: dense planes, exact tests
         hipLaunchKernelGGL(arc_dense_kernel, dim3(kDenseThreads == 512 ? 512 : ctx->n_cu), dim3(kDenseThreads), 0, s, t, g, (const int64_t *)gi.over,
                            (const uint32_t *)gi.n_over, (const uint32_t *)gi.ovf, (const uint4 *)gi.pv,
-                           (const int64_t *)gi.B, (const uint32_t *)gi.mask, gi.res);
+                           (const int64_t *)gi.B, (const uint32_t *)gi.mask, gi.res, (const GroupRec *)gi.grec);
     }
     {
         ECC_TIMED(ctx, s, "flags_kernel");
