@@ -491,6 +491,8 @@ int decode(ecc_ctx *ctx, const void *words_v, int64_t n_words, uint32_t *xy, int
 // ---- n-µs reslicer -------------------------------------------------------------------------
 // Event i opens slices (k_{i-1}, k_i] (k = (t - t_base) / period); each writes bounds[k] = i.
 // Reads t[i-1], t[i] (8 B/event, the neighbour from cache); writes one int64 per slice.
+// A stamp below t_base (possible only in unsorted input, which is flagged) has no slice: it
+// counts as slice -1, so that it never indexes bounds[] below 0.
 __global__ void __launch_bounds__(kThreads)
 reslice_n_us_kernel(const int64_t *__restrict__ t, int64_t n, int64_t period, int64_t *__restrict__ bounds,
                     int64_t max_slices, int64_t *n_slices, int32_t *err) {
@@ -498,12 +500,12 @@ reslice_n_us_kernel(const int64_t *__restrict__ t, int64_t n, int64_t period, in
     const int64_t base = (t0 >= 0 ? t0 / period : -((-t0 + period - 1) / period)) * period;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
         const int64_t ti = t[i];
-        const int64_t k = (ti - base) / period;
+        const int64_t k = ti < base ? -1 : (ti - base) / period;
         int64_t kp = -1;
         if (i > 0) {
             const int64_t tp = t[i - 1];
             if (tp > ti) atomicOr(err, 4);
-            kp = (tp - base) / period;
+            kp = tp < base ? -1 : (tp - base) / period;
         }
         for (int64_t q = kp + 1; q <= k && q < max_slices; ++q) bounds[q] = i;
         if (i == n - 1) {

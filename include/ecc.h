@@ -719,7 +719,9 @@ int ecc_evt_status(ecc_ctx *ctx, ecc_stream_t stream);
  * slice k holds the events with t in [t_base + k*period_us, t_base + (k+1)*period_us), where
  * t_base = floor(t[0] / period_us) * period_us; bounds[k] = index of its first event
  * (bounds[n_slices] = n).  Slices without events are kept (empty ranges), as the reslicer
- * emits one on_new_slice per elapsed period.  t must be non-decreasing.
+ * emits one on_new_slice per elapsed period.  t must be non-decreasing (otherwise
+ * ECC_ERR_UNSORTED_TIME through ecc_evt_status; bounds' contents are then unspecified, but
+ * nothing outside bounds[0 .. max_slices] is written).
  * *n_slices (device int64) = ceil-count of periods spanned; bounds has max_slices + 1 entries
  * and only slices < max_slices are written (ECC_ERR_CAPACITY through ecc_evt_status).
  * The n-events condition (make_n_events(N)) needs no kernel: bounds[k] = min(k*N, n). */
