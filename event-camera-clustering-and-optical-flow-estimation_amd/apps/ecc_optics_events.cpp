@@ -6,6 +6,9 @@
 // --chi X [--steep-min-diff Y]: additionally get_chi_clusters_flat(reach, X, min_pts, Y)
 // (optics.hpp:803-944), printed as "xi_clusters K" and one "begin end" line per pair after the
 // existing output; on the host by default, with --device-order from the reach left on the device.
+// --stats: after all that, "stats_clusters K" and one "begin size cx cy vx vy" line (%.17g) per
+// threshold cluster and, with --chi, "stats_xi K" and one such line per pair; with --device-order
+// these and the "cluster ..." lines come from ecc_cluster_stats_runs / _pairs on the device.
 #include <algorithm>
 #include <cmath>
 
@@ -22,13 +25,28 @@ static std::vector<std::array<int, 2>> read_points(const char *path) {
     return pts;
 }
 
-// The points as one segment of packed u16 xy (translated to the bounding box's corner: distances
-// do not change) through ecc_optics_grid; with xi, the reach stays on the device for ecc_optics_xi.
-using XiPairs = std::vector<std::pair<std::size_t, std::size_t>>;
-static std::vector<ecc::optics::reachability_dist> device_order(const std::vector<std::array<int, 2>> &pts,
-                                                                size_t min_pts, double eps, XiPairs *xi, double chi,
-                                                                double steep_min_diff) {
-    if (pts.empty()) return {};
+// The points as one segment of packed u16 xy through ecc_optics_grid (ordering and threshold cluster
+// ids), ecc_cluster_stats_runs on the order / cluster arrays it leaves on the device and, with xi,
+// ecc_optics_xi on the reach and ecc_cluster_stats_pairs on its pairs.  Points outside
+// [0, 65535]^2 are translated to the bounding box's corner: distances do not change, but the bits
+// of the statistics do, so those are then left to the host loop (stats_exact = false).
+using XiPairs = std::vector<ecc::optics::chi_cluster_indices>;
+using Stats = std::vector<ecc::optics::cluster_stat<2>>;
+struct DeviceOrder {
+    std::vector<ecc::optics::reachability_dist> reach;
+    bool stats_exact = false;
+    Stats clusters, xi_stats;
+    XiPairs xi;
+};
+
+static void check(int rc, const char *what) {
+    if (rc != ECC_OK) throw ecc::Error(rc, what);
+}
+
+static DeviceOrder device_order(const std::vector<std::array<int, 2>> &pts, size_t min_pts, double eps, double thr,
+                                bool with_xi, double chi, double steep_min_diff) {
+    DeviceOrder out;
+    if (pts.empty()) return out;
     if (pts.size() > 8192) {
         std::fprintf(stderr, "--device-order: %zu points, one device segment holds at most 8192\n", pts.size());
         std::exit(1);
@@ -43,31 +61,63 @@ static std::vector<ecc::optics::reachability_dist> device_order(const std::vecto
         std::fprintf(stderr, "--device-order: the points span more than 65535 on an axis\n");
         std::exit(1);
     }
+    out.stats_exact = xmn >= 0 && ymn >= 0 && xmx <= 65535 && ymx <= 65535;
+    if (out.stats_exact) xmn = ymn = 0;
     std::vector<uint32_t> xy(pts.size());
     for (size_t i = 0; i < pts.size(); ++i) xy[i] = ecc::pack_xy(pts[i][0] - xmn, pts[i][1] - ymn);
     ecc::Context &ctx = ecc::Context::default_context();
     ecc::DeviceBuffer d_xy;
     d_xy.upload(xy.data(), xy.size() * 4, ctx.stream());
-    if (!xi)
-        return ecc::optics::compute_reachability_dists_windows(ctx, d_xy.as<uint32_t>(), 1, (int64_t)pts.size(),
-                                                               nullptr, min_pts, eps)[0];
     const int64_t n = (int64_t)pts.size();
-    ecc::DeviceBuffer d_order((size_t)n * 4), d_reach((size_t)n * 8);
-    const int rc = min_pts > 64 ? ECC_ERR_INVALID
-                                : ecc_optics_grid(ctx.get(), d_xy.as<uint32_t>(), 1, n, nullptr, eps, (int32_t)min_pts, 0.0,
-                                                  d_order.as<int32_t>(), d_reach.as<double>(), nullptr, nullptr,
-                                                  ctx.stream());
-    if (rc != ECC_OK) throw ecc::Error(rc, "ecc_optics_grid");
-    *xi = ecc::optics::get_chi_clusters_flat_windows(ctx, d_reach.as<double>(), 1, n, nullptr, chi, min_pts,
-                                                     steep_min_diff)[0];
+    ecc::DeviceBuffer d_order((size_t)n * 4), d_reach((size_t)n * 8), d_cluster((size_t)n * 4), d_ncl(4);
+    check(min_pts > 64 ? ECC_ERR_INVALID
+                       : ecc_optics_grid(ctx.get(), d_xy.as<uint32_t>(), 1, n, nullptr, eps, (int32_t)min_pts, thr,
+                                         d_order.as<int32_t>(), d_reach.as<double>(), d_cluster.as<int32_t>(),
+                                         d_ncl.as<int32_t>(), ctx.stream()),
+          "ecc_optics_grid");
+    out.clusters = ecc::optics::cluster_statistics_windows(ctx, d_xy.as<uint32_t>(), d_order.as<int32_t>(),
+                                                           d_cluster.as<int32_t>(), 1, n, nullptr)[0];
+    if (with_xi) {
+        if (min_pts > (size_t)INT32_MAX) check(ECC_ERR_INVALID, "ecc_optics_xi");
+        ecc::DeviceBuffer d_pairs, d_np(4);
+        int32_t np = 0;
+        // a second pass with the count as capacity when the first guess was too small
+        for (int64_t cap = 64;;) {
+            d_pairs.reserve((size_t)std::max<int64_t>(cap, 1) * 8);
+            check(ecc_optics_xi(ctx.get(), d_reach.as<double>(), 1, n, nullptr, chi, (int32_t)min_pts, steep_min_diff,
+                                d_pairs.as<int32_t>(), cap, d_np.as<int32_t>(), ctx.stream()),
+                  "ecc_optics_xi");
+            d_np.download(&np, 4, ctx.stream());
+            const int rc = ecc_optics_xi_status(ctx.get(), ctx.stream());
+            if (rc == ECC_ERR_CAPACITY && np > cap) {
+                cap = np;
+                continue;
+            }
+            check(rc, "ecc_optics_xi");
+            std::vector<int32_t> pairs((size_t)np * 2);
+            d_pairs.download(pairs.data(), pairs.size() * 4, ctx.stream());
+            ctx.sync();
+            for (int32_t k = 0; k < np; ++k) out.xi.emplace_back((size_t)pairs[(size_t)k * 2], (size_t)pairs[(size_t)k * 2 + 1]);
+            out.xi_stats = ecc::optics::cluster_statistics_windows(ctx, d_xy.as<uint32_t>(), d_order.as<int32_t>(),
+                                                                   d_pairs.as<int32_t>(), cap, d_np.as<int32_t>(), 1, n,
+                                                                   nullptr)[0];
+            break;
+        }
+    }
     std::vector<int32_t> order((size_t)n);
     std::vector<double> reach((size_t)n);
     d_order.download(order.data(), (size_t)n * 4, ctx.stream());
     d_reach.download(reach.data(), (size_t)n * 8, ctx.stream());
     ctx.sync();
-    std::vector<ecc::optics::reachability_dist> out;
-    for (int64_t i = 0; i < n; ++i) out.emplace_back((std::size_t)order[(size_t)i], reach[(size_t)i]);
+    for (int64_t i = 0; i < n; ++i) out.reach.emplace_back((std::size_t)order[(size_t)i], reach[(size_t)i]);
     return out;
+}
+
+static void print_stats(const char *title, const Stats &stats) {
+    std::printf("%s %zu\n", title, stats.size());
+    for (const auto &c : stats)
+        std::printf("%zu %zu %.17g %.17g %.17g %.17g\n", c.begin, c.size, c.centroid[0], c.centroid[1], c.variance[0],
+                    c.variance[1]);
 }
 
 int main(int argc, char **argv) {
@@ -85,29 +135,35 @@ int main(int argc, char **argv) {
         // --eps 0 or negative: estimated (optics.hpp:428-430)
         // --device-order: the whole ordering on the GPU, the points as one ecc_optics_grid segment
         const bool with_xi = has_flag(argc, argv, "--chi"), on_device = has_flag(argc, argv, "--device-order");
+        const bool with_stats = has_flag(argc, argv, "--stats");
         const double chi = opt_double(argc, argv, "--chi", 0.0);
         const double steep_min_diff = opt_double(argc, argv, "--steep-min-diff", 0.0);
-        XiPairs xi;
-        auto reach = on_device ? device_order(pts, min_pts, eps, with_xi ? &xi : nullptr, chi, steep_min_diff)
-                               : ecc::optics::compute_reachability_dists(pts, min_pts, eps);
-        if (with_xi && !(on_device && !pts.empty()))
-            xi = ecc::optics::get_chi_clusters_flat(reach, chi, min_pts, steep_min_diff);
-        auto clusters = ecc::optics::get_cluster_indices(reach, thr);
+        DeviceOrder dev;
+        if (on_device) dev = device_order(pts, min_pts, eps, thr, with_xi, chi, steep_min_diff);
+        const bool from_device = on_device && !pts.empty();
+        const auto reach = from_device ? dev.reach : ecc::optics::compute_reachability_dists(pts, min_pts, eps);
+        const XiPairs xi = !with_xi      ? XiPairs{}
+                           : from_device ? dev.xi
+                                         : ecc::optics::get_chi_clusters_flat(reach, chi, min_pts, steep_min_diff);
+        // get_cluster_points (:470) and the statistics loop (:472-527)
+        const Stats clusters = from_device && dev.stats_exact ? dev.clusters
+                                                              : ecc::optics::cluster_statistics(pts, reach, thr);
         std::printf("points %zu clusters %zu\n", pts.size(), clusters.size());
-        for (size_t c = 0; c < clusters.size(); ++c) {
-            double sx = 0, sy = 0;
-            for (size_t i : clusters[c]) { sx += pts[i][0]; sy += pts[i][1]; }
-            const double m = (double)clusters[c].size(), cx = sx / m, cy = sy / m;
-            double vx = 0, vy = 0;
-            for (size_t i : clusters[c]) { vx += (pts[i][0] - cx) * (pts[i][0] - cx); vy += (pts[i][1] - cy) * (pts[i][1] - cy); }
-            std::printf("cluster %zu size %zu centroid (%.4f, %.4f) variance (%.4f, %.4f)\n", c, clusters[c].size(), cx, cy, vx / m, vy / m);
-        }
+        for (size_t c = 0; c < clusters.size(); ++c)
+            std::printf("cluster %zu size %zu centroid (%.4f, %.4f) variance (%.4f, %.4f)\n", c, clusters[c].size,
+                        clusters[c].centroid[0], clusters[c].centroid[1], clusters[c].variance[0], clusters[c].variance[1]);
         std::printf("order");
         for (const auto &r : reach) std::printf(" %zu:%.17g", r.point_index, r.reach_dist);
         std::printf("\n");
         if (with_xi) {
             std::printf("xi_clusters %zu\n", xi.size());
             for (const auto &c : xi) std::printf("%zu %zu\n", c.first, c.second);
+        }
+        if (with_stats) {
+            print_stats("stats_clusters", clusters);
+            if (with_xi)
+                print_stats("stats_xi", from_device && dev.stats_exact ? dev.xi_stats
+                                                                       : ecc::optics::cluster_statistics(pts, reach, xi));
         }
     } catch (const ecc::Error &e) {
         std::fprintf(stderr, "%s\n", e.what());

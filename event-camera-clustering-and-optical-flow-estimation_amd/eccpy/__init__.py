@@ -67,6 +67,16 @@ class Corner(C.Structure):
 CORNER_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("label", np.int32)])
 
 
+class ClusterStat(C.Structure):  # ecc_cluster_stat, 40 bytes
+    _fields_ = [("begin", C.c_int32), ("size", C.c_int32), ("cx", C.c_double), ("cy", C.c_double),
+                ("vx", C.c_double), ("vy", C.c_double)]
+
+
+CLUSTER_STAT_DTYPE = np.dtype([("begin", np.int32), ("size", np.int32), ("cx", np.float64), ("cy", np.float64),
+                               ("vx", np.float64), ("vy", np.float64)])
+assert CLUSTER_STAT_DTYPE.itemsize == C.sizeof(ClusterStat) == 40
+
+
 class TrackerCfg(C.Structure):
     _fields_ = [("max_distance", C.c_float), ("max_frames", C.c_int32),
                 ("history_size", C.c_int32), ("frames_to_skip", C.c_int32),
@@ -199,6 +209,10 @@ _sigs = {
     "ecc_optics_xi_status": (C.c_int, [P, P]),
     "ecc_optics_xi_resident_segments": (C.c_int, [P, P]),
     "ecc_optics_xi_host": (C.c_int, [P, i64, C.c_double, i32, C.c_double, P, i64, P]),
+    "ecc_cluster_stats_runs": (C.c_int, [P, P, P, P, i64, i64, P, P, i64, P, P]),
+    "ecc_cluster_stats_pairs": (C.c_int, [P, P, P, P, i64, P, i64, i64, P, P, P]),
+    "ecc_cluster_stats_status": (C.c_int, [P, P]),
+    "ecc_cluster_stats_host": (C.c_int, [P, P, i64, P, i64, P]),
     "ecc_device_sync": (C.c_int, []),
     "ecc_reslice_n_us": (C.c_int, [P, P, i64, i64, P, i64, P, P]),
     "ecc_dist_available": (C.c_int, []),
@@ -545,6 +559,24 @@ class Context:
         check(lib.ecc_optics_xi_resident_segments(self.ctx, C.addressof(v)), "ecc_optics_xi_resident_segments")
         return v.value
 
+    def cluster_stats_runs(self, xy: DeviceArray, order: DeviceArray, cluster: DeviceArray, n_segs: int, stride: int,
+                           counts_in, stats: DeviceArray, cap: int, n_stats: DeviceArray):
+        """Size, centroid and variance of every threshold cluster (maximal run of equal ids in optics_grid's
+        cluster array) of every segment in one launch: stats CLUSTER_STAT_DTYPE[n_segs * cap], run k of
+        segment s at s * cap + k; n_stats int32[n_segs]."""
+        check(lib.ecc_cluster_stats_runs(self.ctx, xy.ptr, order.ptr, cluster.ptr, n_segs, stride, _ptr(counts_in),
+                                         stats.ptr, cap, n_stats.ptr, self.stream), "ecc_cluster_stats_runs")
+
+    def cluster_stats_pairs(self, xy: DeviceArray, order: DeviceArray, pairs: DeviceArray, pair_cap: int,
+                            n_pairs: DeviceArray, n_segs: int, stride: int, counts_in, stats: DeviceArray):
+        """The same for optics_xi's {begin, end} pairs (pairs, pair_cap, n_pairs as optics_xi's clusters, cap,
+        n_clusters): stats CLUSTER_STAT_DTYPE[n_segs * pair_cap], pair k of segment s at s * pair_cap + k."""
+        check(lib.ecc_cluster_stats_pairs(self.ctx, xy.ptr, order.ptr, pairs.ptr, pair_cap, n_pairs.ptr, n_segs, stride,
+                                          _ptr(counts_in), stats.ptr, self.stream), "ecc_cluster_stats_pairs")
+
+    def cluster_stats_status(self) -> int:
+        return lib.ecc_cluster_stats_status(self.ctx, self.stream)
+
     # ---- 8. RAW ingest
     def evt_decode(self, fmt: int, words: DeviceArray, n_words: int, xy: DeviceArray | None,
                    t: DeviceArray | None, p: DeviceArray | None, cap: int, n_out: DeviceArray,
@@ -765,6 +797,20 @@ def optics_xi_host(reach, chi: float, min_pts: int, steep_area_min_diff: float =
     check(lib.ecc_optics_xi_host(r.ctypes.data, r.size, chi, min_pts, steep_area_min_diff, out.ctypes.data, cap,
                                  C.addressof(n_out)), "ecc_optics_xi_host")
     return out[:n_out.value]
+
+
+def cluster_stats_host(xy, order, pairs):
+    """Size, centroid and variance of the {begin, end} intervals `pairs` (k, 2) of one ordered plot on the
+    host (no GPU): xy packed uint32[n], order int32[n] -> (CLUSTER_STAT_DTYPE[k], status); status is
+    ERR_INVALID when a pair or an order entry inside one lay outside the plot (those records have size 0)."""
+    xy = np.ascontiguousarray(xy, np.uint32)
+    order = np.ascontiguousarray(order, np.int32)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    assert xy.size == order.size
+    out = np.zeros(len(pairs), CLUSTER_STAT_DTYPE)
+    rc = lib.ecc_cluster_stats_host(xy.ctypes.data, order.ctypes.data, xy.size, pairs.ctypes.data, len(pairs),
+                                    out.ctypes.data)
+    return out, rc
 
 
 def pack_xy(x, y) -> np.ndarray:

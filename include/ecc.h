@@ -612,6 +612,51 @@ int ecc_optics_xi_resident_segments(ecc_ctx *ctx, int32_t *per_cu);
 int ecc_optics_xi_host(const double *reach, int64_t n, double chi, int32_t min_pts,
                        double steep_area_min_diff, int32_t *clusters, int64_t cap, int64_t *n_out);
 
+/* ecc_cluster_stats_*: size, centroid and per-axis variance of every cluster of every segment, in
+ * one launch (one workgroup per segment), on the arrays ecc_optics_grid / ecc_optics_xi leave on the
+ * device: the product line "j,size,cx,cy,devx,devy" of the reference's OPTICS event driver.
+ * Reference: OPT/test/cluster_event_data.cpp:472-527 over the points of optics::get_cluster_points
+ *   (OPT/include/optics/optics.hpp:692-721 threshold clusters, :724-774 xi pairs), literally: a
+ *   cluster is an interval [begin, end] of one segment's ordered plot, its points pts[order[begin..
+ *   end]] in plot order; with m = end - begin + 1: sx = sum (double)x, cx = sx / (double)m, then
+ *   sequentially in plot order d = (double)x - cx; acc += d * d; vx = acc / (double)m — the same
+ *   for y; fp64, no fusion.  The sums are exact integers; the variance chain is walked serially.
+ * xy, order, seg_counts: DEVICE, laid out as ecc_downsample_hash and ecc_optics_grid leave them: xy
+ *   packed u16 at s*seg_stride + j, order segment-local indices, seg_counts NULL = full segments;
+ *   1 <= seg_stride <= 8192.
+ * ecc_cluster_stats_runs: `cluster` is ecc_optics_grid's id array; a cluster is a maximal run of
+ *   equal ids (a run starts at i == 0 or where cluster[i] != cluster[i-1]: get_cluster_indices
+ *   :674-690 for the grid's output, the clamped first id included).  Run k of segment s goes to
+ *   stats[s*cap + k]; n_stats[s] = the number of runs, even above cap; only the first cap are
+ *   written and nothing else of `stats` is touched.
+ * ecc_cluster_stats_pairs: pairs / n_pairs are ecc_optics_xi's clusters / n_clusters and pair_cap its
+ *   cap; intervals may nest, repeat or be single points.  Pair k < min(n_pairs[s], pair_cap) of
+ *   segment s goes to stats[s*pair_cap + k], in the same order.
+ * ecc_cluster_stats_status (of the last call of either form; synchronises `stream`):
+ *   ECC_ERR_INVALID if an order entry lay outside [0, seg_counts[s]) or a pair had begin > end,
+ *   begin < 0 or end >= seg_counts[s] — such an entry is never used as an index, the affected
+ *   records are {begin, 0, 0, 0, 0, 0} and other segments are unaffected; else ECC_ERR_CAPACITY if
+ *   a segment had more runs than cap; ECC_ERR_INVALID for NULL ctx.
+ * ECC_ERR_INVALID (before any launch): NULL ctx; NULL xy / order / cluster / stats / n_stats
+ * (runs) or xy / order / pairs / n_pairs / stats (pairs) with n_segs > 0; n_segs < 0; cap or
+ * pair_cap < 0; seg_stride outside [1, 8192].  n_segs == 0: ECC_OK after the same range checks. */
+typedef struct ecc_cluster_stat { int32_t begin, size; double cx, cy, vx, vy; } ecc_cluster_stat; /* 40 B */
+int ecc_cluster_stats_runs(ecc_ctx *ctx, const uint32_t *xy, const int32_t *order, const int32_t *cluster,
+                           int64_t n_segs, int64_t seg_stride, const int32_t *seg_counts,
+                           ecc_cluster_stat *stats, int64_t cap, int32_t *n_stats, ecc_stream_t stream);
+int ecc_cluster_stats_pairs(ecc_ctx *ctx, const uint32_t *xy, const int32_t *order, const int32_t *pairs,
+                            int64_t pair_cap, const int32_t *n_pairs, int64_t n_segs, int64_t seg_stride,
+                            const int32_t *seg_counts, ecc_cluster_stat *stats, ecc_stream_t stream);
+int ecc_cluster_stats_status(ecc_ctx *ctx, ecc_stream_t stream);
+/* ecc_cluster_stats_host (cluster_event_data.cpp:472-527): the same loop for the n_pairs intervals
+ * {begin, end} of ONE plot in HOST memory, of any n <= INT32_MAX, on the host (no GPU, no context):
+ * the route for a single ecc_optics_f64 result.  stats: HOST [n_pairs].  ECC_ERR_INVALID: n < 0,
+ * n_pairs < 0, NULL xy / order with n > 0, NULL pairs / stats with n_pairs > 0 (nothing written);
+ * or, after every record is written, a pair outside [0, n) or with begin > end, or an interval
+ * holding an order entry outside [0, n): those records are {begin, 0, 0, 0, 0, 0}. */
+int ecc_cluster_stats_host(const uint32_t *xy, const int32_t *order, int64_t n, const int32_t *pairs,
+                           int64_t n_pairs, ecc_cluster_stat *stats);
+
 /* DBSCAN over ONE point cloud of any size in 1-3 dimensions: DBSCANSimpleCluster::extract
  * (PCC/DBSCAN_simple.h:27-90) with its radiusSearch (:118-142) on the reference's own input type,
  * a float pcl::PointXYZ cloud (ecc_dbscan_cloud_f32, dim 3 = x,y,z; the differences in float as

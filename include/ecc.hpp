@@ -13,6 +13,9 @@
 //                                    OPT/include/optics/optics.hpp:413-565  ecc::optics::compute_reachability_dists
 //                                                                  (runtime N instead of the template N)
 //   optics::get_chi_clusters_flat    optics.hpp:803-944             ecc::optics::get_chi_clusters_flat[_windows]
+//   optics::get_cluster_points       optics.hpp:692-721, 760-774    ecc::optics::get_cluster_points
+//   per-cluster size, centroid, variance  OPT/test/cluster_event_data.cpp:472-527
+//                                                                  ecc::optics::cluster_statistics[_windows]
 //   optics::get_cluster_indices / epsilon_estimation
 //                                    optics.hpp:674-690, 369-387   ecc::optics::...
 //   DBSCANSimpleCluster / DBSCANPrecompCluster::{setInputCloud, setClusterTolerance,
@@ -438,6 +441,48 @@ std::vector<std::vector<std::pair<std::size_t, std::size_t>>> get_chi_clusters_f
     Context &ctx, const double *device_reach, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
     double chi, std::size_t min_pts, double steep_area_min_diff = 0.0);
 
+// optics.hpp:692-721 and :760-774 — the points of every threshold cluster / of every xi pair
+// (positions begin..end of the ordered plot, inclusive), in plot order.  Error(ECC_ERR_INVALID) for
+// a point_index outside `points` or a pair outside the plot (the reference asserts or reads past).
+using chi_cluster_indices = std::pair<std::size_t, std::size_t>;  // :50
+template <typename T, std::size_t dimension>
+std::vector<std::vector<std::array<T, dimension>>> get_cluster_points(
+    const std::vector<reachability_dist> &reach_dists, double reachability_threshold,
+    const std::vector<std::array<T, dimension>> &points);
+template <typename T, std::size_t dimension>
+std::vector<std::vector<std::array<T, dimension>>> get_cluster_points(
+    const std::vector<reachability_dist> &reach_dists, const std::vector<chi_cluster_indices> &clusters,
+    const std::vector<std::array<T, dimension>> &points);
+
+// OPT/test/cluster_event_data.cpp:472-527 — what the reference's event driver prints per cluster:
+// its first position in the ordered plot, its size, the centroid sum / size and the per-axis
+// variance sum((x - centroid)^2) / size, accumulated in plot order in fp64 as the driver does.
+template <std::size_t dimension>
+struct cluster_stat {
+    std::size_t begin, size;
+    std::array<double, dimension> centroid, variance;
+};
+template <typename T, std::size_t dimension>
+std::vector<cluster_stat<dimension>> cluster_statistics(const std::vector<std::array<T, dimension>> &points,
+                                                        const std::vector<reachability_dist> &reach_dists,
+                                                        double reachability_threshold);
+template <typename T, std::size_t dimension>
+std::vector<cluster_stat<dimension>> cluster_statistics(const std::vector<std::array<T, dimension>> &points,
+                                                        const std::vector<reachability_dist> &reach_dists,
+                                                        const std::vector<chi_cluster_indices> &clusters);
+// The same for many windows of packed u16 xy points on the DEVICE, on the arrays ecc_optics_grid
+// (device_order, device_cluster) and ecc_optics_xi (device_pairs, pair_cap, device_n_pairs) leave
+// there: one launch for all segments (ecc_cluster_stats_runs / _pairs; seg_stride <= 8192,
+// device_seg_counts null = full segments).  One vector per segment, in run / pair order.
+// Synchronises the context's stream.
+std::vector<std::vector<cluster_stat<2>>> cluster_statistics_windows(
+    Context &ctx, const uint32_t *device_xy, const int32_t *device_order, const int32_t *device_cluster,
+    int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts);
+std::vector<std::vector<cluster_stat<2>>> cluster_statistics_windows(
+    Context &ctx, const uint32_t *device_xy, const int32_t *device_order, const int32_t *device_pairs,
+    int64_t pair_cap, const int32_t *device_n_pairs, int64_t n_segs, int64_t seg_stride,
+    const int32_t *device_seg_counts);
+
 }  // namespace optics
 
 // ------------------------------------------------------------------------------ DBSCAN
@@ -513,6 +558,85 @@ double epsilon_estimation(const std::vector<std::array<T, dimension>> &points, s
     const double space_per_minpts = (volume / static_cast<double>(points.size())) * static_cast<double>(min_pts);
     const double unit_ball = std::sqrt(std::pow(M_PI, d)) / std::tgamma(d / 2.0 + 1.0);
     return std::pow(space_per_minpts / unit_ball, 1.0 / d);
+}
+
+// optics.hpp:692-721: fplus::elems_at_idxs(cluster_indices, points) per threshold cluster
+template <typename T, std::size_t dimension>
+std::vector<std::vector<std::array<T, dimension>>> get_cluster_points(
+    const std::vector<reachability_dist> &reach_dists, double reachability_threshold,
+    const std::vector<std::array<T, dimension>> &points) {
+    std::vector<std::vector<std::array<T, dimension>>> result;
+    for (const auto &cluster_indices : get_cluster_indices(reach_dists, reachability_threshold)) {
+        result.emplace_back();
+        result.back().reserve(cluster_indices.size());
+        for (std::size_t i : cluster_indices) {
+            if (i >= points.size()) throw Error(ECC_ERR_INVALID, "get_cluster_points");
+            result.back().push_back(points[i]);
+        }
+    }
+    return result;
+}
+
+// optics.hpp:724-739 and :760-774: reach_dists[c.first .. c.second].point_index per pair
+template <typename T, std::size_t dimension>
+std::vector<std::vector<std::array<T, dimension>>> get_cluster_points(
+    const std::vector<reachability_dist> &reach_dists, const std::vector<chi_cluster_indices> &clusters,
+    const std::vector<std::array<T, dimension>> &points) {
+    std::vector<std::vector<std::array<T, dimension>>> result;
+    result.reserve(clusters.size());
+    for (const auto &c : clusters) {
+        if (c.first > c.second || c.second >= reach_dists.size()) throw Error(ECC_ERR_INVALID, "get_cluster_points");
+        result.emplace_back();
+        result.back().reserve(c.second - c.first + 1);
+        for (std::size_t idx = c.first; idx <= c.second; idx++) {
+            const std::size_t i = reach_dists[idx].point_index;
+            if (i >= points.size()) throw Error(ECC_ERR_INVALID, "get_cluster_points");
+            result.back().push_back(points[i]);
+        }
+    }
+    return result;
+}
+
+// cluster_event_data.cpp:493-526 for one cluster's points
+template <typename T, std::size_t dimension>
+cluster_stat<dimension> cluster_points_statistics(std::size_t begin,
+                                                  const std::vector<std::array<T, dimension>> &cluster_points) {
+    cluster_stat<dimension> r{begin, cluster_points.size(), {}, {}};
+    for (std::size_t a = 0; a < dimension; a++) {
+        double sum = 0.0, deviation = 0.0;
+        for (const auto &p : cluster_points) sum += p[a];
+        r.centroid[a] = sum / cluster_points.size();
+        for (const auto &p : cluster_points) {
+            const double deviation_diff = p[a] - r.centroid[a];
+            deviation += deviation_diff * deviation_diff;
+        }
+        r.variance[a] = deviation / cluster_points.size();
+    }
+    return r;
+}
+
+template <typename T, std::size_t dimension>
+std::vector<cluster_stat<dimension>> cluster_statistics(const std::vector<std::array<T, dimension>> &points,
+                                                        const std::vector<reachability_dist> &reach_dists,
+                                                        double reachability_threshold) {
+    std::vector<cluster_stat<dimension>> result;
+    std::size_t begin = 0;
+    for (const auto &cluster_points : get_cluster_points(reach_dists, reachability_threshold, points)) {
+        result.push_back(cluster_points_statistics(begin, cluster_points));
+        begin += cluster_points.size();
+    }
+    return result;
+}
+
+template <typename T, std::size_t dimension>
+std::vector<cluster_stat<dimension>> cluster_statistics(const std::vector<std::array<T, dimension>> &points,
+                                                        const std::vector<reachability_dist> &reach_dists,
+                                                        const std::vector<chi_cluster_indices> &clusters) {
+    std::vector<cluster_stat<dimension>> result;
+    const auto cluster_points = get_cluster_points(reach_dists, clusters, points);
+    for (std::size_t k = 0; k < clusters.size(); k++)
+        result.push_back(cluster_points_statistics(clusters[k].first, cluster_points[k]));
+    return result;
 }
 }  // namespace optics
 
