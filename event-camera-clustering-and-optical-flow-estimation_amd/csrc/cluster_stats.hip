@@ -28,7 +28,6 @@ constexpr int kNT = 256;
 constexpr int kMaxStride = 8192;
 constexpr int kMaskWords = kMaxStride / 64;
 constexpr int kMaxBlocks = 2048;  // 8 per CU on 256 CUs; LDS admits 3 (runs) or 4 (pairs) at stride 8192
-constexpr int kFlagWord = 14;     // ctx->flags[14]: a segment had more runs than cap; [15]: invalid order entry or pair
 
 __device__ __forceinline__ uint32_t axis_of(uint32_t w, int sh) { return (w >> sh) & 0xffffu; }
 
@@ -74,8 +73,7 @@ __global__ __launch_bounds__(kNT) void cluster_stats_kernel(const uint32_t *__re
     const int tid = (int)threadIdx.x, lane = ecc::lane_id(), wave = tid >> 6;
 
     for (int64_t s = blockIdx.x; s < n_segs; s += gridDim.x) {
-        int n = seg_counts ? seg_counts[s] : (int)stride;
-        n = n < 0 ? 0 : (n > (int)stride ? (int)stride : n);
+        const int n = ecc::seg_points(seg_counts, stride, s);
         const int64_t seg = s * stride;
         if (tid < kMaskWords) s_start[tid] = 0, s_bad[tid] = 0;
         if (tid == 0) s_any_bad = 0;
@@ -163,14 +161,14 @@ int launch(ecc_ctx *ctx, bool runs, const uint32_t *xy, const int32_t *order, co
     hipStream_t s = ecc::as_stream(stream);
     const unsigned grid = (unsigned)std::min<int64_t>(n_segs, kMaxBlocks);
     const size_t lds = (size_t)stride * 4 + (runs ? ecc::align_up((size_t)stride * 2, 4) : 0);
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + kFlagWord, 0, 8, s), "memset(cluster stats err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->dev->cluster_stats, 0, 8, s), "memset(cluster stats err)");
     ECC_TIMED(ctx, s, runs ? "cluster_stats_runs_kernel" : "cluster_stats_pairs_kernel");
     if (runs)
         hipLaunchKernelGGL(cluster_stats_kernel<true>, dim3(grid), dim3(kNT), lds, s, xy, order, src, n_src, n_segs,
-                           stride, seg_counts, stats, cap, n_stats, ctx->flags + kFlagWord);
+                           stride, seg_counts, stats, cap, n_stats, ctx->dev->cluster_stats);
     else
         hipLaunchKernelGGL(cluster_stats_kernel<false>, dim3(grid), dim3(kNT), lds, s, xy, order, src, n_src, n_segs,
-                           stride, seg_counts, stats, cap, n_stats, ctx->flags + kFlagWord);
+                           stride, seg_counts, stats, cap, n_stats, ctx->dev->cluster_stats);
     ECC_CHECK_LAUNCH(ctx, "cluster_stats");
     return ECC_OK;
 }
@@ -199,8 +197,6 @@ ECC_API int ecc_cluster_stats_pairs(ecc_ctx *ctx, const uint32_t *xy, const int3
 ECC_API int ecc_cluster_stats_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f[2] = {0, 0};
-    hipStream_t s = ecc::as_stream(stream);
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(f, ctx->flags + kFlagWord, 8, hipMemcpyDeviceToHost, s), "read cluster stats err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");
+    if (int rc = ecc::read_dev_words(ctx, ctx->dev->cluster_stats, 2, f, ecc::as_stream(stream))) return rc;
     return f[1] ? ECC_ERR_INVALID : (f[0] ? ECC_ERR_CAPACITY : ECC_OK);
 }

@@ -46,10 +46,9 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kBuildUnroll = 8;
-// ctx->flags[10]: the tag of the last sort phase that saw decreasing time (every sort phase gets
-// a fresh host-side tag, so a stale word never matches a later call); flags[0]: the verdict
-// sae_prefix_kernel published for the last finished call (pending word == its prepare's tag)
-constexpr int kSortPendingWord = 10;
+// DevWords::sort_pending holds the tag of the last sort phase that saw decreasing time (every sort
+// phase gets a fresh host-side tag, so a stale word never matches a later call); fast_verdict the
+// verdict sae_prefix_kernel published for the last finished call (pending word == its prepare's tag)
 // the flag pass's dynamic LDS limit: 160 KiB less its static LDS (ctot[kFlagQuads][4], 128 B)
 constexpr size_t kFlagDynLdsMax = 160 * 1024 - 256;
 constexpr int kArcThreads = 512;  // 8 waves: one lane per window pixel (484) when staging
@@ -1815,7 +1814,7 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
         }
         ECC_TIMED(ctx, s, "slice_sort_kernel");
         hipLaunchKernelGGL(kern, dim3((unsigned)g.n_slices), dim3(kSortThreads), lds, s, xy, t, g,
-                           so, first_border, ctx->flags + kSortPendingWord, st->prep_tag,
+                           so, first_border, &ctx->dev->sort_pending, st->prep_tag,
                            (phases & 2) ? gi.n_over : nullptr, zero_nms_err, gi.grec);
     }
     {
@@ -1846,7 +1845,7 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
         const int64_t HW = (int64_t)g.W * g.H;
         const unsigned blocks = (unsigned)((HW + kPrefixPix - 1) / kPrefixPix);
         hipLaunchKernelGGL(sae_prefix_kernel, dim3(blocks), dim3(kThreads), 0, s, g, n_groups,
-                           (const uint32_t *)gi.mask, gi.B, sae, ctx->flags, ctx->flags + kSortPendingWord,
+                           (const uint32_t *)gi.mask, gi.B, sae, &ctx->dev->fast_verdict, &ctx->dev->sort_pending,
                            st->prep_tag, (phases & 1) ? nullptr : gi.n_over, (phases & 1) ? nullptr : zero_nms_err);
     }
     {
@@ -1957,7 +1956,7 @@ static int fast_detect_nms_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_
     // the NMS error word is zeroed by the call's first kernel (n > 0 here: nms_candidates gave a
     // buffer): the sort kernel, or in a finish-only call the SAE prefix
     int rc = fast_detect_phases(ctx, xy, t, n, cfg, sae, corner_flags, nullptr, phases, stream, cand, n_cand,
-                                ctx->flags + 1);
+                                &ctx->dev->nms);
     if (rc) return rc;
     rc = ecc::nms_greedy(ctx, cand, n_cand, n, cfg->slice_events, cfg->width, cfg->height, box_size, cap, out,
                          out_count, s);
@@ -1996,9 +1995,8 @@ ECC_API int ecc_fast_detect_status(ecc_ctx *ctx, ecc_stream_t stream) {
     const CornerState *st = state_of(ctx);
     if (st->status_src == 0) return ECC_OK;
     int32_t w = 0;
-    const int32_t *src = st->status_src == 1 ? ctx->flags + kSortPendingWord : ctx->flags;
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&w, src, 4, hipMemcpyDeviceToHost, ecc::as_stream(stream)), "read err flag");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(ecc::as_stream(stream)), "sync");
+    const int32_t *src = st->status_src == 1 ? &ctx->dev->sort_pending : &ctx->dev->fast_verdict;
+    if (int rc = ecc::read_dev_words(ctx, src, 1, &w, ecc::as_stream(stream))) return rc;
     const bool bad = st->status_src == 1 ? w == st->prep_tag : w != 0;
     return bad ? ECC_ERR_UNSORTED_TIME : ECC_OK;
 }

@@ -36,6 +36,12 @@ int ws_reserve(ecc_ctx *ctx, size_t bytes) {
     return ECC_OK;
 }
 
+int read_dev_words(ecc_ctx *ctx, const int32_t *src, int n, int32_t *out, hipStream_t s) {
+    ECC_CHECK_HIP(ctx, hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToHost, s), "read device words");
+    ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");
+    return ECC_OK;
+}
+
 static hipEvent_t pool_get(ecc_ctx *ctx) {
     if (!ctx->event_pool.empty()) {
         hipEvent_t e = ctx->event_pool.back();
@@ -134,8 +140,8 @@ ECC_API int ecc_ctx_create(ecc_ctx **out, int device) {
     ecc_ctx *ctx = new (std::nothrow) ecc_ctx();
     if (!ctx) return ECC_ERR_NOMEM;
     ctx->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipMalloc(&ctx->flags, 256) != hipSuccess ||
-        hipMemset(ctx->flags, 0, 256) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || hipMalloc(&ctx->dev, sizeof(ecc::DevWords)) != hipSuccess ||
+        hipMemset(ctx->dev, 0, sizeof(ecc::DevWords)) != hipSuccess) {
         delete ctx;
         return ECC_ERR_HIP;
     }
@@ -155,7 +161,7 @@ ECC_API int ecc_ctx_destroy(ecc_ctx *ctx) {
     ecc::corner_state_release(ctx);
     ecc::nms_state_release(ctx);
     if (ctx->ws) hipFree(ctx->ws);
-    if (ctx->flags) hipFree(ctx->flags);
+    if (ctx->dev) hipFree(ctx->dev);
     delete ctx;
     return ECC_OK;
 }

@@ -27,17 +27,17 @@
 // walks the 3x3 cells instead (exact integer eps test), so the whole DBSCAN of a segment reads
 // its 4-B points once and writes its labels once (+ the duplicate memberships).
 #include "eps_grid.hpp"
+#include "run_bitmap.hpp"
 
 #include <cmath>
 #include <cstdlib>
 
 namespace {
 
+namespace runbm = ecc::runbm;
 constexpr int kThreads = 1024;
 constexpr int kMaxPts = 16384;
 constexpr int kMaxComp = 4096;
-constexpr int kFlagWord = 4;  // ctx->flags[4]: bit 1 capacity
-constexpr int kLeftWord = 11;  // ctx->flags[11]: segments dbscan_run_kernel left to dbscan_grid_kernel
 
 bool getenv_flag(const char *name) {
     const char *v = std::getenv(name);
@@ -148,7 +148,7 @@ dbscan_extract_kernel(int64_t n_segs, int64_t stride, const int32_t *__restrict_
     __shared__ int s_kept, s_bad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int64_t s = blockIdx.x; s < n_segs; s += gridDim.x) {
-        const int m = seg_counts ? min(seg_counts[s], (int)stride) : (int)stride;
+        const int m = ecc::seg_points(seg_counts, stride, s);
         const int64_t base = s * stride;
         if (offsets[base] < 0 || offsets[base + m] > nbr_len) {  // lists not (fully) present
             if (threadIdx.x == 0) {
@@ -343,8 +343,7 @@ dbscan_grid_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t stri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int64_t s = blockIdx.x; s < n_segs; s += gridDim.x) {
         if (left && n_clusters[s] != -1) continue;  // uniform: done by the row-run kernel
-        int m = seg_counts ? seg_counts[s] : (int)stride;
-        m = m < 0 ? 0 : (m > (int)stride ? (int)stride : m);
+        const int m = ecc::seg_points(seg_counts, stride, s);
         const int64_t base = s * stride;
 #if ECC_DBSCAN_PROFILE
         unsigned long long db_t_ = wall_clock64();
@@ -613,10 +612,9 @@ dbscan_grid_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t stri
 
 // ---- row-run DBSCAN (distinct-pixel segments: downsample windows) -------------------------------
 // A downsample window's representatives are distinct pixels, so the segment is an occupancy
-// bitmap over its bounding box (eps.hip's row-run form): word w of row y holds 32 pixels and the
-// number of points in the words before it, so a pixel's raster rank is one word read + popc (the
-// point's id in the union-find below).  A second bitmap marks the core points.
-//   counts:  the disk's rows as prefix differences (eps_run_counts_kernel's count, self included);
+// bitmap over its bounding box (run_bitmap.hpp), in which a pixel's raster rank is one word read
+// + popc (the point's id in the union-find below).  A second bitmap marks the core points.
+//   counts:  the disk's rows as prefix differences (runbm::chord_count, self included);
 //   unions:  the core points within eps of core point p in a row are a chord [x - w, x + w] of
 //            that row.  Consecutive core points of one row within eps of each other (gap <= e)
 //            are united left to right (a chain); a chord is at most 2e + 1 wide, so its core
@@ -669,21 +667,13 @@ dbscan_run_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t strid
     __shared__ int wsum[kThreads / 64];
     __shared__ int s_dup, s_kept, s_nc, s_nl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int kW = kThreads / 64;
     if (tid == 0) {
         wd[kDrWords] = make_uint2(0u, 0u);
         cw[kDrWords] = 0u;
     }
-    for (int a = tid; a < kDrHw && a <= e_int; a += kThreads) {  // exact integer square roots
-        const uint32_t v = r2i - (uint32_t)(a * a);
-        uint32_t h = (uint32_t)sqrtf((float)v);
-        while (h * h > v) --h;
-        while ((h + 1) * (h + 1) <= v) ++h;
-        hwt[a] = (uint16_t)h;
-    }
+    runbm::fill_half_widths(hwt, kDrHw, e_int, r2i, tid, kThreads);
     for (int64_t s = blockIdx.x; s < n_segs; s += gridDim.x) {
-        int m = seg_counts ? seg_counts[s] : (int)stride;
-        m = m < 0 ? 0 : (m > (int)stride ? (int)stride : m);
+        const int m = ecc::seg_points(seg_counts, stride, s);
         const int64_t base = s * stride;
 #if ECC_DBSCAN_PROFILE
         unsigned long long db_t_ = wall_clock64();
@@ -700,25 +690,12 @@ dbscan_run_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t strid
                 xmx = max(xmx, ecc::xy_x(v[u])); ymx = max(ymx, ecc::xy_y(v[u]));
             }
         }
-        xmn = ecc::wave_min_i32(xmn); ymn = ecc::wave_min_i32(ymn);  // DPP
-        xmx = ecc::wave_max_i32(xmx); ymx = ecc::wave_max_i32(ymx);
-        if (lane == 0) {
-            box[wave][0] = xmn; box[wave][1] = ymn;
-            box[wave][2] = xmx; box[wave][3] = ymx;
-        }
         if (tid == 0) s_dup = 0;
-        __syncthreads();
-        xmn = box[0][0]; ymn = box[0][1]; xmx = box[0][2]; ymx = box[0][3];
-#pragma unroll
-        for (int w = 1; w < kW; ++w) {
-            xmn = min(xmn, box[w][0]); ymn = min(ymn, box[w][1]);
-            xmx = max(xmx, box[w][2]); ymx = max(ymx, box[w][3]);
-        }
-        const int Wb = m ? xmx - xmn + 1 : 1, H = m ? ymx - ymn + 1 : 1;
-        const int WW = (Wb >> 5) + 1;
-        const int64_t words64 = (int64_t)H * WW;
-        bool leftover = words64 > kDrWords || e_int >= kDrHw;  // uniform
-        const int words = leftover ? 0 : (int)words64;
+        const runbm::Box bx = runbm::block_box<kThreads / 64>(box, m, xmn, ymn, xmx, ymx, lane, wave);  // a barrier
+        xmn = bx.xmn, ymn = bx.ymn;
+        const int Wb = bx.Wb, H = bx.H, WW = bx.WW;
+        bool leftover = bx.words() > kDrWords || e_int >= kDrHw;  // uniform
+        const int words = leftover ? 0 : (int)bx.words();
         for (int w = opaque_lane(tid); w < words; w += kThreads) {
             wd[w] = make_uint2(0u, 0u);
             cw[w] = 0u;
@@ -729,9 +706,7 @@ dbscan_run_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t strid
 #pragma unroll
             for (int u = 0; u < kDrPer; ++u) {
                 if (u * kThreads + tid >= m) break;
-                const int x = ecc::xy_x(v[u]) - xmn, y = ecc::xy_y(v[u]) - ymn;
-                const uint32_t bit = 1u << (x & 31);
-                if (atomicOr(&wd[y * WW + (x >> 5)].x, bit) & bit) s_dup = 1;
+                if (runbm::set_pixel(wd, bx, ecc::xy_x(v[u]) - xmn, ecc::xy_y(v[u]) - ymn)) s_dup = 1;
             }
         }
         __syncthreads();
@@ -744,27 +719,10 @@ dbscan_run_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t strid
             __syncthreads();
             continue;
         }
-        {  // points before each word (thread t: words [t * per, t * per + per))
-            const int per = (words + kThreads - 1) / kThreads;
-            const int w0 = opaque_lane(tid) * per, w1 = min(w0 + per, words);
-            int loc = 0;
-            for (int w = w0; w < w1; ++w) loc += __popc(wd[w].x);
-            const int inc = ecc::wave_incl_scan(loc);
-            if (lane == 63) wsum[opaque_lane(wave)] = inc;
-            __syncthreads();
-            int off = inc - loc;
-            for (int w = 0; w < opaque_lane(wave); ++w) off += wsum[w];
-            for (int w = w0; w < w1; ++w) {
-                wd[w].y = (uint32_t)off;
-                off += __popc(wd[w].x);
-            }
-        }
+        runbm::prefix_words(wd, words, wsum, opaque_lane(tid), lane, opaque_lane(wave), kThreads);  // a barrier
         __syncthreads();
         // raster rank of the pixel at (x, y) of the box (a set bit)
-        auto rank_at = [&](int x, int y) -> int {
-            const uint2 q = wd[y * WW + (x >> 5)];
-            return (int)q.y + __popc(q.x & ((1u << (x & 31)) - 1u));
-        };
+        auto rank_at = [&](int x, int y) -> int { return runbm::rank_at(wd, bx, x, y); };
         const int amax = min(e_int, H - 1);
         // the point of lane tid's slot u, re-read (an L2 hit) in the phases after the counts: its
         // register copy would not fit the 64 VGPRs beside the union batches
@@ -777,24 +735,7 @@ dbscan_run_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t strid
             const int j = u * kThreads + opaque_lane(tid);
             if (j >= m) break;
             const int x = ecc::xy_x(v[u]) - xmn, y = ecc::xy_y(v[u]) - ymn;
-            int cnt = 0;
-#pragma unroll 4
-            for (int a = 0; a <= amax; ++a) {  // (unrolled: four rows' word loads in flight)
-                const int hw = hwt[a];
-                const int xl = max(x - hw, 0), xh = min(x + hw + 1, Wb);
-                const uint32_t ml = (1u << (xl & 31)) - 1u, mh = (1u << (xh & 31)) - 1u;
-                const int cl = xl >> 5, ch = xh >> 5;
-#pragma unroll
-                for (int sgn = 0; sgn < 2; ++sgn) {
-                    if (sgn && a == 0) break;
-                    const int yy = sgn ? y - a : y + a;
-                    const bool ok = (unsigned)yy < (unsigned)H;
-                    const int rb = yy * WW;
-                    const uint2 lo = wd[ok ? rb + cl : kDrWords], hi = wd[ok ? rb + ch : kDrWords];
-                    cnt += (int)(hi.y - lo.y) + __popc(hi.x & mh) - __popc(lo.x & ml);
-                }
-            }
-            const bool core = cnt >= min_pts;
+            const bool core = runbm::chord_count(wd, kDrWords, bx, hwt, x, y, amax) >= min_pts;
             const int r = rank_at(x, y);
             parent[r] = core ? r : -1;
             if (core) atomicOr(&cw[y * WW + (x >> 5)], 1u << (x & 31));
@@ -1180,7 +1121,7 @@ ECC_API int ecc_dbscan_extract(ecc_ctx *ctx, int64_t n_segs, int64_t seg_stride,
         return ECC_ERR_INVALID;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
-    int32_t *err = ctx->flags + kFlagWord;
+    int32_t *err = &ctx->dev->dbscan;
     ECC_CHECK_HIP(ctx, hipMemsetAsync(err, 0, 4, s), "memset(dbscan err)");
     if (n_dups) ECC_CHECK_HIP(ctx, hipMemsetAsync(n_dups, 0, 8, s), "memset(n_dups)");
     if (n_segs == 0) return ECC_OK;
@@ -1207,7 +1148,7 @@ ECC_API int ecc_dbscan_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, in
     if (n_segs > 0 && (!xy || !labels || !n_clusters || !n_dups || (dup_cap > 0 && !dups))) return ECC_ERR_INVALID;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
-    int32_t *err = ctx->flags + kFlagWord;
+    int32_t *err = &ctx->dev->dbscan;
     ECC_CHECK_HIP(ctx, hipMemsetAsync(err, 0, 4, s), "memset(dbscan err)");
     ECC_CHECK_HIP(ctx, hipMemsetAsync(n_dups, 0, 8, s), "memset(n_dups)");
     if (n_segs == 0) return ECC_OK;
@@ -1221,7 +1162,7 @@ ECC_API int ecc_dbscan_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, in
     // the row-run kernel first (distinct-pixel segments whose bitmap fits its LDS); the grid kernel
     // takes what it leaves, and exits at once when it leaves nothing
     const bool run = e_int < kDrHw && !getenv_flag("ECC_DBSCAN_GRID_ONLY");
-    int32_t *left = ctx->flags + kLeftWord;
+    int32_t *left = &ctx->dev->dbscan_left;
     if (run) {
         ECC_CHECK_HIP(ctx, hipMemsetAsync(left, 0, 4, s), "memset(dbscan leftovers)");
         ECC_TIMED(ctx, s, "dbscan_run_kernel");
@@ -1245,9 +1186,7 @@ ECC_API int ecc_dbscan_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, in
 ECC_API int ecc_dbscan_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f = 0;
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&f, ctx->flags + kFlagWord, 4, hipMemcpyDeviceToHost, ecc::as_stream(stream)),
-                  "read dbscan err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(ecc::as_stream(stream)), "sync");
+    if (int rc = ecc::read_dev_words(ctx, &ctx->dev->dbscan, 1, &f, ecc::as_stream(stream))) return rc;
     if (f & 4) return ECC_ERR_INVALID;  // a neighbour index outside its segment (ecc_dbscan_extract)
     return (f & 2) ? ECC_ERR_CAPACITY : ECC_OK;
 }

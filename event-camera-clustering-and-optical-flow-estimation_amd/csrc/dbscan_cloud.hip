@@ -34,7 +34,6 @@ namespace {
 
 using ecc::rgrid::Grid;
 using ecc::rgrid::kThreads;
-constexpr int kFlagWord = 8;  // ctx->flags[8]: bit 1 duplicate capacity exceeded
 constexpr uint64_t kSentinel = (1ull << 62) - 1;
 
 __device__ __forceinline__ int uf_find(int *parent, int x) {
@@ -293,7 +292,7 @@ int run_phases(ecc_ctx *ctx, const T *pts, const ecc::rgrid::Ws &w, Cloud c, cha
     uint8_t *core_s = reinterpret_cast<uint8_t *>(carve((size_t)n));
     uint8_t *more = reinterpret_cast<uint8_t *>(carve((size_t)n));
     void *tmp = carve(sort_tmp);
-    int32_t *err = ctx->flags + kFlagWord;
+    int32_t *err = &ctx->dev->dbscan_cloud;
     const unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
     const Grid *g = w.grid;
     ECC_CHECK_HIP(ctx, hipMemsetAsync(c_size, 0, (size_t)n * 4, s), "memset(c_size)");
@@ -345,7 +344,7 @@ int dbscan_cloud(ecc_ctx *ctx, const T *pts, int64_t n, int32_t dim, double eps,
     if (!n_clusters || !n_dups || (n > 0 && (!pts || !labels)) || (dup_cap > 0 && !dups)) return ECC_ERR_INVALID;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + kFlagWord, 0, 4, s), "memset(dbscan cloud err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(&ctx->dev->dbscan_cloud, 0, 4, s), "memset(dbscan cloud err)");
     ECC_CHECK_HIP(ctx, hipMemsetAsync(n_dups, 0, 8, s), "memset(n_dups)");
     if (n == 0) {
         ECC_CHECK_HIP(ctx, hipMemsetAsync(n_clusters, 0, 4, s), "memset(n_clusters)");
@@ -401,8 +400,6 @@ ECC_API int ecc_dbscan_cloud_f64(ecc_ctx *ctx, const double *pts, int64_t n, int
 ECC_API int ecc_dbscan_cloud_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f = 0;
-    hipStream_t s = ecc::as_stream(stream);
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&f, ctx->flags + kFlagWord, 4, hipMemcpyDeviceToHost, s), "read dbscan err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");
+    if (int rc = ecc::read_dev_words(ctx, &ctx->dev->dbscan_cloud, 1, &f, ecc::as_stream(stream))) return rc;
     return (f & 2) ? ECC_ERR_CAPACITY : ECC_OK;
 }

@@ -7,9 +7,11 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ecc.h"
+#include "grid_geometry.hpp"
 
 #define ECC_API extern "C" __attribute__((visibility("default")))
 
@@ -23,6 +25,10 @@ struct EccTimingPair {
     hipEvent_t a, b;
 };
 
+namespace ecc {
+struct DevWords;
+}
+
 struct ecc_ctx {
     int device = 0;
     int n_cu = 256;  // compute units of the device (persistent-grid sizing)
@@ -35,11 +41,48 @@ struct ecc_ctx {
     // Scratch workspace, grown on demand (never inside a capture: call once eagerly first).
     void *ws = nullptr;
     size_t ws_bytes = 0;
-    // Small pinned-free device words: [0] unsorted-time flag of the last fast_detect.
-    int32_t *flags = nullptr;
+    // The kernels' status words and small device-side results (ecc::DevWords below).
+    ecc::DevWords *dev = nullptr;
 };
 
 namespace ecc {
+
+// Device memory of the context that kernels write and the *_status calls read back: one member
+// per user, zeroed by ecc_ctx_create.  Each entry point clears its own member before it launches.
+struct DevWords {
+    int32_t fast_verdict;      // corners.hip: unsorted-time verdict of the last fast_detect
+    int32_t nms;               // nms.hip (and the fused corner + NMS phases): bit 0 capacity, bit 1 outside
+    int32_t eps_lists;         // eps.hip: the lists disagree with the counts, or nbr_cap exceeded
+    int32_t evt;               // evt.hip: bit 1 capacity, bit 2 unsorted t
+    int32_t dbscan;            // dbscan.hip: bit 1 capacity, bit 2 a neighbour index outside its segment
+    int32_t kmeans_frame;      // kmeans.hip: a point outside the count frame
+    int32_t radius[2];         // radius.hip: [0] bit 1 list capacity; radius_grid.hpp: [1] non-finite input
+    int32_t dbscan_cloud;      // dbscan_cloud.hip: bit 1 duplicate capacity
+    int32_t eps_left;          // eps.hip: segments the row-run counts left to the candidate walk
+    int32_t sort_pending;      // corners.hip: tag of the last sort phase that saw decreasing time
+    int32_t dbscan_left;       // dbscan.hip: segments dbscan_run_kernel left to dbscan_grid_kernel
+    int32_t optics_xi[2];      // optics_xi.hip: [0] more pairs than cap, [1] the workspace check fired
+    int32_t cluster_stats[2];  // cluster_stats.hip: [0] more runs than cap, [1] invalid order entry or pair
+    int64_t box_keys[6];       // radius_grid.hpp: bounding-box keys (3 min, 3 max)
+    rgrid::Grid grid;          // radius_grid.hpp: the cloud grid's geometry
+};
+static_assert(std::is_trivially_copyable<DevWords>::value, "DevWords is memset and copied bytewise");
+static_assert(alignof(DevWords) >= 8, "the int64 keys and the grid's doubles");
+
+// Copies n words at src (inside *ctx->dev) to out and waits for the stream.  Returns status.
+int read_dev_words(ecc_ctx *ctx, const int32_t *src, int n, int32_t *out, hipStream_t s);
+
+// A run of segments of `stride` slots each; segment s holds its first seg_points(s) slots
+// (counts == null: all of them).
+struct SegView {
+    const int32_t *counts;
+    int64_t n_segs, stride;
+};
+__device__ __forceinline__ int seg_points(const int32_t *counts, int64_t stride, int64_t s) {
+    const int m = counts ? counts[s] : (int)stride;
+    return m < 0 ? 0 : (m > (int)stride ? (int)stride : m);
+}
+__device__ __forceinline__ int seg_points(const SegView &sv, int64_t s) { return seg_points(sv.counts, sv.stride, s); }
 
 // Records the HIP error on the context and returns ECC_ERR_HIP.
 int hip_fail(ecc_ctx *ctx, hipError_t e, const char *what);

@@ -19,9 +19,11 @@
 // Algorithmic bytes: 4 B/point in + 4 B/point (count) [+ 8 B core distance] out; lists: + 4 B
 // per neighbour out.
 #include "eps_grid.hpp"
+#include "run_bitmap.hpp"
 
 namespace {
 
+namespace runbm = ecc::runbm;
 using ecc::epsg::CellGrid;
 using ecc::epsg::kCells;
 using ecc::epsg::kNT;
@@ -29,18 +31,9 @@ using ecc::buffer_load_u32;
 using ecc::buffer_view;
 using ecc::xy_x;
 using ecc::xy_y;
+using ecc::seg_points;
+using ecc::SegView;
 constexpr int kMaxPts = 16384;
-constexpr int kLeftWord = 9;  // ctx->flags[9]: segments the row-run counts left to the candidate walk
-
-struct SegView {
-    const int32_t *counts;
-    int64_t n_segs, stride;
-};
-
-__device__ __forceinline__ int seg_points(const SegView &sv, int64_t s) {
-    int m = sv.counts ? sv.counts[s] : (int)sv.stride;
-    return m < 0 ? 0 : (m > (int)sv.stride ? (int)sv.stride : m);
-}
 
 // Counts (+ core distances when K > 0: the K smallest d^2 kept, K >= min_pts).  Dynamic LDS:
 // cend[kCells + 1] | spt[stride] | sidx[stride] and, when kStage, st_cnt[stride] (u16) |
@@ -119,18 +112,13 @@ eps_counts_kernel(const uint32_t *__restrict__ xy, SegView sv, int e_int, uint32
 
 // Row-run form.  A segment's points are distinct pixels whenever it is a downsample window (one
 // representative per hash bucket, and a pixel always hashes to the same bucket), so the segment is
-// an occupancy bitmap over its bounding box, one bit per pixel, 32 pixels a word, each word paired
-// with the number of points in the words before it (row-major).  The points of row y in [xl, xh)
-// then number prefix(y, xh) - prefix(y, xl), with prefix(y, x) = base[word] + popc(bits[word]
-// below x): a query's count is a sum over the 2*eps + 1 rows of the disk (half-width w(dy) =
-// floor(sqrt(floor(eps^2) - dy^2)), the same integer test d^2 <= floor(eps^2) as the candidate
-// walk), two LDS reads per row, no candidate loop and no test.  (Core distances by walking each
-// row's run bit by bit measured 0.68 -> 0.92 ms at OPTICS eps 10; see K > 0 below.)  The bitmap
-// of a 346 x 260
-// sensor is 3120 words (25 KB): four 8-wave workgroups per CU share the CU's LDS, so one
-// segment's set-up barriers overlap the others' queries.  A segment whose bitmap exceeds
-// kRunWords or that repeats a pixel is left to eps_counts_kernel (marked by counts[base] = -1,
-// counted in *left).
+// an occupancy bitmap over its bounding box (run_bitmap.hpp) and a query's count is a sum of
+// prefix differences over the 2*eps + 1 rows of the disk: two LDS reads per row, no candidate
+// loop and no test.  (Core distances by walking each row's run bit by bit measured 0.68 -> 0.92 ms
+// at OPTICS eps 10; see K > 0 below.)  The bitmap of a 346 x 260 sensor is 3120 words (25 KB):
+// four 8-wave workgroups per CU share the CU's LDS, so one segment's set-up barriers overlap the
+// others' queries.  A segment whose bitmap exceeds kRunWords or that repeats a pixel is left to
+// eps_counts_kernel (marked by counts[base] = -1, counted in *left).
 constexpr int kRT = 512;
 constexpr int kRunWords = 4864;  // (bits, prefix) pairs: 38 KB, four workgroups per CU
 constexpr int kHwTab = 512;      // eps < 512 (larger eps: the candidate walk)
@@ -148,20 +136,13 @@ eps_run_counts_kernel(const uint32_t *__restrict__ xy, SegView sv, int e_int, ui
     __shared__ int box[kRT / 64][4];
     __shared__ int wsum[kRT / 64];
     __shared__ int dup[2];  // by segment parity: reset one segment ahead, behind two barriers
-    __shared__ uint16_t hwt[kHwTab];  // disk half-widths floor(sqrt(floor(eps^2) - a^2)), a < kHwTab
+    __shared__ uint16_t hwt[kHwTab];  // disk half-widths, a < kHwTab
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int kW = kRT / 64;
     if (tid == 0) {
         wd[kRunWords] = make_uint2(0u, 0u);
         dup[0] = dup[1] = 0;
     }
-    for (int a = tid; a < kHwTab && a <= e_int; a += kRT) {  // exact integer square roots
-        const uint32_t v = r2i - (uint32_t)(a * a);
-        uint32_t h = (uint32_t)sqrtf((float)v);
-        while (h * h > v) --h;
-        while ((h + 1) * (h + 1) <= v) ++h;
-        hwt[a] = (uint16_t)h;
-    }
+    runbm::fill_half_widths(hwt, kHwTab, e_int, r2i, tid, kRT);
     int par = 0;
     for (int64_t s = blockIdx.x; s < sv.n_segs; s += gridDim.x, par ^= 1) {
         if (tid == 0) dup[par ^ 1] = 0;  // last read in the previous segment, before its barrier 6
@@ -174,22 +155,10 @@ eps_run_counts_kernel(const uint32_t *__restrict__ xy, SegView sv, int e_int, ui
             xmn = min(xmn, xy_x(v)); ymn = min(ymn, xy_y(v));
             xmx = max(xmx, xy_x(v)); ymx = max(ymx, xy_y(v));
         }
-        xmn = ecc::wave_min_i32(xmn); ymn = ecc::wave_min_i32(ymn);  // DPP
-        xmx = ecc::wave_max_i32(xmx); ymx = ecc::wave_max_i32(ymx);
-        if (lane == 0) {
-            box[wave][0] = xmn; box[wave][1] = ymn;
-            box[wave][2] = xmx; box[wave][3] = ymx;
-        }
-        __syncthreads();  // 1
-        xmn = box[0][0]; ymn = box[0][1]; xmx = box[0][2]; ymx = box[0][3];
-#pragma unroll
-        for (int w = 1; w < kW; ++w) {
-            xmn = min(xmn, box[w][0]); ymn = min(ymn, box[w][1]);
-            xmx = max(xmx, box[w][2]); ymx = max(ymx, box[w][3]);
-        }
-        const int Wb = m ? xmx - xmn + 1 : 1, H = m ? ymx - ymn + 1 : 1;
-        const int WW = (Wb >> 5) + 1;  // words per row: x == Wb (a run's end) still has a word
-        const int64_t words = (int64_t)H * WW;
+        const runbm::Box bx = runbm::block_box<kRT / 64>(box, m, xmn, ymn, xmx, ymx, lane, wave);  // barrier 1
+        xmn = bx.xmn, ymn = bx.ymn;
+        const int H = bx.H, WW = bx.WW;
+        const int64_t words = bx.words();
         bool leftover = words > kRunWords;  // uniform
         if (!leftover) {
             for (int w = tid; w < words; w += kRT) wd[w] = make_uint2(0u, 0u);
@@ -198,10 +167,7 @@ eps_run_counts_kernel(const uint32_t *__restrict__ xy, SegView sv, int e_int, ui
         if (!leftover) {
             for (int q = tid; q < m; q += kRT) {
                 const uint32_t v = buffer_load_u32(seg, (uint32_t)q * 4u);
-                const int x = xy_x(v) - xmn, y = xy_y(v) - ymn;
-                const uint32_t bit = 1u << (x & 31);
-                const uint32_t old = atomicOr(&wd[y * WW + (x >> 5)].x, bit);
-                if (old & bit) dup[par] = 1;
+                if (runbm::set_pixel(wd, bx, xy_x(v) - xmn, xy_y(v) - ymn)) dup[par] = 1;
             }
         }
         __syncthreads();  // 3
@@ -212,20 +178,8 @@ eps_run_counts_kernel(const uint32_t *__restrict__ xy, SegView sv, int e_int, ui
                 atomicAdd(left, 1);
             }
         } else {
-            if (K == 0) {  // prefix of the word popcounts: thread t takes words [t * per, t * per + per)
-                const int per = (int)((words + kRT - 1) / kRT);
-                const int w0 = tid * per, w1 = min(w0 + per, (int)words);
-                int loc = 0;
-                for (int w = w0; w < w1; ++w) loc += __popc(wd[w].x);
-                const int inc = ecc::wave_incl_scan(loc);
-                if (lane == 63) wsum[wave] = inc;
-                __syncthreads();  // 4
-                int off = inc - loc;
-                for (int w = 0; w < wave; ++w) off += wsum[w];
-                for (int w = w0; w < w1; ++w) {
-                    wd[w].y = (uint32_t)off;
-                    off += __popc(wd[w].x);
-                }
+            if (K == 0) {
+                runbm::prefix_words(wd, (int)words, wsum, tid, lane, wave, kRT);  // barrier 4
                 __syncthreads();  // 5
             }
             // queries in segment order: lane q's results at base + q (coalesced)
@@ -283,23 +237,7 @@ eps_run_counts_kernel(const uint32_t *__restrict__ xy, SegView sv, int e_int, ui
                     }
                 } else if (q < m) {
                     const uint32_t v = buffer_load_u32(seg, (uint32_t)q * 4u);
-                    const int x = xy_x(v) - xmn, y = xy_y(v) - ymn;
-#pragma unroll 4
-                    for (int a = 0; a <= amax; ++a) {
-                        const int hw = hwt[a];  // a broadcast read; no loop-carried state
-                        const int xl = max(x - hw, 0), xh = min(x + hw + 1, Wb);
-                        const uint32_t ml = (1u << (xl & 31)) - 1u, mh = (1u << (xh & 31)) - 1u;
-                        const int cl = xl >> 5, ch = xh >> 5;
-#pragma unroll
-                        for (int sgn = 0; sgn < 2; ++sgn) {
-                            if (sgn && a == 0) break;
-                            const int yy = sgn ? y - a : y + a;
-                            const bool ok = (unsigned)yy < (unsigned)H;
-                            const int rb = yy * WW;
-                            const uint2 lo = wd[ok ? rb + cl : kRunWords], hi = wd[ok ? rb + ch : kRunWords];
-                            cnt += (int)(hi.y - lo.y) + __popc(hi.x & mh) - __popc(lo.x & ml);
-                        }
-                    }
+                    cnt = runbm::chord_count(wd, kRunWords, bx, hwt, xy_x(v) - xmn, xy_y(v) - ymn, amax);
                 }
                 counts[base + q] = cnt;
                 if (K > 0) {
@@ -495,7 +433,7 @@ ECC_API int ecc_eps_counts(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int
     // candidate walk, which exits at once without any; other cases take the candidate walk whole.
     const bool run = K == 0 ? e_int < kHwTab : (K <= 8 && e_int < 32);
     if (run) {
-        int32_t *left = ctx->flags + kLeftWord;
+        int32_t *left = &ctx->dev->eps_left;
         ECC_CHECK_HIP(ctx, hipMemsetAsync(left, 0, 4, s), "memset(eps leftovers)");
         {
             using RunKern = void (*)(const uint32_t *, SegView, int, uint32_t, int, int32_t *, double *, int32_t *);
@@ -538,7 +476,7 @@ ECC_API int ecc_eps_lists(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int6
     hipStream_t s = ecc::as_stream(stream);
     rc = ecc::exclusive_scan_i32_i64(ctx, counts, n, offsets, reinterpret_cast<int64_t *>(ctx->ws), s);
     if (rc) return rc;
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + 2, 0, 4, s), "memset(eps err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(&ctx->dev->eps_lists, 0, 4, s), "memset(eps err)");
     SegView sv{seg_counts, n_segs, seg_stride};
     const int r2i = (int)std::floor(eps * eps), e_int = (int)std::floor(eps);
     const size_t grid_words = (size_t)((kCells + 1 + seg_stride + (seg_stride + 1) / 2 + 1) & ~1ll);
@@ -550,7 +488,7 @@ ECC_API int ecc_eps_lists(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int6
     {
         ECC_TIMED(ctx, s, "eps_lists_kernel");
         hipLaunchKernelGGL(eps_lists_kernel, dim3(grid), dim3(kNT), lds, s, xy, sv, e_int, (uint32_t)r2i,
-                           (const int64_t *)offsets, nbr, nbr_cap, ctx->flags + 2);
+                           (const int64_t *)offsets, nbr, nbr_cap, &ctx->dev->eps_lists);
     }
     ECC_CHECK_LAUNCH(ctx, "eps_lists_kernel");
     return ECC_OK;
@@ -562,7 +500,6 @@ ECC_API int ecc_eps_total(ecc_ctx *ctx, const int64_t *offsets, int64_t n, int64
     hipStream_t s = ecc::as_stream(stream);
     int32_t err = 0;
     ECC_CHECK_HIP(ctx, hipMemcpyAsync(total, offsets + n, 8, hipMemcpyDeviceToHost, s), "read total");
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&err, ctx->flags + 2, 4, hipMemcpyDeviceToHost, s), "read err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");
+    if (int rc = ecc::read_dev_words(ctx, &ctx->dev->eps_lists, 1, &err, s)) return rc;  // waits for both copies
     return err ? ECC_ERR_CAPACITY : ECC_OK;
 }

@@ -29,7 +29,6 @@ namespace {
 constexpr int kThreads = 256;
 // Each lane owns 64 B of words: 16 EVT 2.0 or 32 EVT 3.0 words (F::kPer); a workgroup owns a
 // chunk of kThreads * F::kPer words.
-constexpr int kFlagWord = 3;               // ctx->flags[3]: bit 1 capacity, bit 2 unsorted t
 
 // ---- EVT 3.0 -------------------------------------------------------------------------------
 // 16-bit words, type = w >> 12:
@@ -459,7 +458,7 @@ int decode(ecc_ctx *ctx, const void *words_v, int64_t n_words, uint32_t *xy, int
     S *gsum = reinterpret_cast<S *>(ws + o_gs), *gcarry = reinterpret_cast<S *>(ws + o_gc);
     int64_t *goff = reinterpret_cast<int64_t *>(ws + o_go);
     uint4 *lanepre = reinterpret_cast<uint4 *>(ws + o_lp);
-    int32_t *err = ctx->flags + kFlagWord;
+    int32_t *err = &ctx->dev->evt;
     ECC_CHECK_HIP(ctx, hipMemsetAsync(err, 0, 4, s), "memset(evt err)");
     if (n_chunks == 0) {
         if (n_out) ECC_CHECK_HIP(ctx, hipMemsetAsync(n_out, 0, 8, s), "memset(n_out)");
@@ -533,9 +532,7 @@ ECC_API int ecc_evt_decode(ecc_ctx *ctx, int32_t format, const void *words, int6
 ECC_API int ecc_evt_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f = 0;
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&f, ctx->flags + kFlagWord, 4, hipMemcpyDeviceToHost, ecc::as_stream(stream)),
-                  "read evt err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(ecc::as_stream(stream)), "sync");
+    if (int rc = ecc::read_dev_words(ctx, &ctx->dev->evt, 1, &f, ecc::as_stream(stream))) return rc;
     if (f & 4) return ECC_ERR_UNSORTED_TIME;
     if (f & 2) return ECC_ERR_CAPACITY;
     return ECC_OK;
@@ -546,7 +543,7 @@ ECC_API int ecc_reslice_n_us(ecc_ctx *ctx, const int64_t *t, int64_t n, int64_t 
     if (!ctx || n < 0 || period_us <= 0 || max_slices < 0 || !bounds || (n > 0 && !t)) return ECC_ERR_INVALID;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
-    int32_t *err = ctx->flags + kFlagWord;
+    int32_t *err = &ctx->dev->evt;
     ECC_CHECK_HIP(ctx, hipMemsetAsync(err, 0, 4, s), "memset(evt err)");
     if (n == 0) {
         ECC_CHECK_HIP(ctx, hipMemsetAsync(bounds, 0, 8, s), "bounds[0]");

@@ -2505,7 +2505,6 @@ ECC_API int ecc_kmeans_refcompat_f32(ecc_ctx *ctx, const float *xy, int64_t n, f
 // Counts are additive over shards, and a Lloyd pass over a count image adds exactly the integer
 // sums of the points it counts, so summing the shards' images once and running every pass
 // locally gives each rank the single-GPU centroids.
-constexpr int kKmFlagWord = 5;  // ctx->flags[5]: a point outside the count frame (3: evt, 4: dbscan)
 
 __global__ void kmeans_set_wh_kernel(uint32_t *wh, uint32_t w, uint32_t h) {
     wh[0] = w;
@@ -2522,7 +2521,7 @@ ECC_API int ecc_kmeans_counts_xy16(ecc_ctx *ctx, const uint32_t *xy, int64_t n_s
     const int64_t cells = (int64_t)frame_w * frame_h;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + kKmFlagWord, 0, 4, s), "memset(kmeans err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(&ctx->dev->kmeans_frame, 0, 4, s), "memset(kmeans err)");
     if (segs.n_segs == 0) {
         ECC_CHECK_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)cells * 4, s), "memset(counts)");
         return ECC_OK;
@@ -2547,7 +2546,7 @@ ECC_API int ecc_kmeans_counts_xy16(ecc_ctx *ctx, const uint32_t *xy, int64_t n_s
         ECC_TIMED(ctx, s, "kmeans_count_kernel");
         hipLaunchKernelGGL(kmeans_count_kernel, dim3(count_grid(parts, slots)), dim3(kHistThreads), kHistChunk * 4, s,
                            xy, segs, (const uint32_t *)nullptr, 0, parts, slots, partial, wh, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                           (uint32_t)frame_w, (uint32_t)frame_h, ctx->flags + kKmFlagWord);
+                           (uint32_t)frame_w, (uint32_t)frame_h, &ctx->dev->kmeans_frame);
     }
     {
         ECC_TIMED(ctx, s, "kmeans_count_sum_kernel");
@@ -2561,9 +2560,7 @@ ECC_API int ecc_kmeans_counts_xy16(ecc_ctx *ctx, const uint32_t *xy, int64_t n_s
 ECC_API int ecc_kmeans_counts_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f = 0;
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&f, ctx->flags + kKmFlagWord, 4, hipMemcpyDeviceToHost, ecc::as_stream(stream)),
-                  "read kmeans flag");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(ecc::as_stream(stream)), "sync");
+    if (int rc = ecc::read_dev_words(ctx, &ctx->dev->kmeans_frame, 1, &f, ecc::as_stream(stream))) return rc;
     return f ? ECC_ERR_INVALID : ECC_OK;
 }
 

@@ -346,7 +346,7 @@ int nms_greedy(ecc_ctx *ctx, const uint32_t *cand, const int32_t *n_cand, int64_
     const int gw = (width + cs - 1) / cs, gh = (height + cs - 1) / cs;
     ECC_TIMED(ctx, s, "nms_kernel");
     hipLaunchKernelGGL(nms_greedy_kernel, dim3((unsigned)n_slices), dim3(kGridThreads), (size_t)(gw + 2) * (gh + 2) * 4,
-                       s, cand, n_cand, slice_events, width, height, half, gw, gh, cap, out, out_count, ctx->flags + 1);
+                       s, cand, n_cand, slice_events, width, height, half, gw, gh, cap, out, out_count, &ctx->dev->nms);
     return ECC_OK;
 }
 }  // namespace ecc
@@ -362,7 +362,7 @@ ECC_API int ecc_corner_nms(ecc_ctx *ctx, const uint32_t *xy, const uint8_t *corn
     if (n_slices > INT32_MAX) return ECC_ERR_INVALID;
     hipStream_t s = ecc::as_stream(stream);
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + 1, 0, 4, s), "memset(nms err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(&ctx->dev->nms, 0, 4, s), "memset(nms err)");
     uint32_t *cand = nullptr;
     int32_t *n_cand = nullptr;
     int rc = ecc::nms_candidates(ctx, n, slice_events, width, height, box_size, &cand, &n_cand);
@@ -379,7 +379,7 @@ ECC_API int ecc_corner_nms(ecc_ctx *ctx, const uint32_t *xy, const uint8_t *corn
         ECC_TIMED(ctx, s, "nms_kernel");
         hipLaunchKernelGGL(nms_kernel, dim3((unsigned)n_slices), dim3(kThreads), 0, s, xy,
                            corner_flags, n, slice_events, width, height, box_size / 2, cap, out,
-                           out_count, ctx->flags + 1);
+                           out_count, &ctx->dev->nms);
     }
     ECC_CHECK_LAUNCH(ctx, "nms_kernel");
     return ECC_OK;
@@ -408,9 +408,7 @@ ECC_API int ecc_corner_pack(ecc_ctx *ctx, const ecc_corner *in, const int32_t *c
 ECC_API int ecc_corner_nms_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f = 0;
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&f, ctx->flags + 1, 4, hipMemcpyDeviceToHost, ecc::as_stream(stream)),
-                  "read nms flag");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(ecc::as_stream(stream)), "sync");
+    if (int rc = ecc::read_dev_words(ctx, &ctx->dev->nms, 1, &f, ecc::as_stream(stream))) return rc;
     if (f & 2) return ECC_ERR_INVALID;
     return (f & 1) ? ECC_ERR_CAPACITY : ECC_OK;
 }

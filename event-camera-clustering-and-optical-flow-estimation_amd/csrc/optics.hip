@@ -197,8 +197,7 @@ optics_grid_kernel(const uint32_t *__restrict__ xy, int64_t n_segs, int64_t stri
     __shared__ int wsum[kNT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int64_t s = blockIdx.x; s < n_segs; s += gridDim.x) {
-        int m = seg_counts ? seg_counts[s] : (int)stride;
-        m = m < 0 ? 0 : (m > (int)stride ? (int)stride : m);
+        const int m = ecc::seg_points(seg_counts, stride, s);
         const int64_t base = s * stride;
         const CellGrid g = ecc::epsg::bin_cells(xy, base, m, e_int, r2i, cend, spt, sidx, red, false, true);
         // core distances (:286-299): the (min_pts-1)-th smallest d^2 of the ball, self included

@@ -29,7 +29,6 @@ constexpr int kWaves = 4;  // waves (= segments in flight) per workgroup
 constexpr int kNT = kWaves * 64;
 constexpr int kLdsSdas = 128;    // SDA entries per wave held in LDS (3 KiB per wave)
 constexpr int kMaxBlocks = 1024;  // 4096 waves: 16 per CU on 256 CUs
-constexpr int kFlagWord = 12;     // ctx->flags[12]: a segment had more pairs than cap; [13]: the workspace check fired (NaN plots)
 
 __device__ __forceinline__ double uniform_lane(double v, int l) {
     return __longlong_as_double(ecc::lane_value64(__double_as_longlong(v), l));
@@ -198,8 +197,7 @@ __global__ __launch_bounds__(kNT) void optics_xi_kernel(const double *__restrict
     SdaList L{s_be[wave], s_mib[wave], s_gb[wave], spill + wg * spill_entries * 3, spill_entries, 0};
 
     for (int64_t s = wg; s < n_segs; s += n_waves) {
-        int n = seg_counts ? seg_counts[s] : (int)stride;
-        n = __builtin_amdgcn_readfirstlane(n < 0 ? 0 : (n > (int)stride ? (int)stride : n));
+        const int n = __builtin_amdgcn_readfirstlane(ecc::seg_points(seg_counts, stride, s));
         Plot P{reach + s * stride, n, 0.0};
         int64_t n_out = 0;
         bool guard = false;
@@ -299,11 +297,11 @@ ECC_API int ecc_optics_xi(ecc_ctx *ctx, const double *reach, int64_t n_segs, int
     const int64_t spill_entries = std::max<int64_t>(0, seg_stride / 2 + 2 - kLdsSdas);
     const size_t ws_bytes = (size_t)grid * kWaves * (size_t)spill_entries * 24;
     if (int rc = ecc::ws_reserve(ctx, std::max<size_t>(ws_bytes, 64)); rc != ECC_OK) return rc;
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + kFlagWord, 0, 8, s), "memset(optics xi err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->dev->optics_xi, 0, 8, s), "memset(optics xi err)");
     ECC_TIMED(ctx, s, "optics_xi_kernel");
     hipLaunchKernelGGL(optics_xi_kernel, dim3(grid), dim3(kNT), 0, s, reach, n_segs, seg_stride, seg_counts, chi,
                        (int)min_pts, steep_area_min_diff, clusters, cap, n_clusters,
-                       reinterpret_cast<uint64_t *>(ctx->ws), spill_entries, ctx->flags + kFlagWord);
+                       reinterpret_cast<uint64_t *>(ctx->ws), spill_entries, ctx->dev->optics_xi);
     ECC_CHECK_LAUNCH(ctx, "optics_xi");
     return ECC_OK;
 }
@@ -311,9 +309,7 @@ ECC_API int ecc_optics_xi(ecc_ctx *ctx, const double *reach, int64_t n_segs, int
 ECC_API int ecc_optics_xi_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f[2] = {0, 0};
-    hipStream_t s = ecc::as_stream(stream);
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(f, ctx->flags + kFlagWord, 8, hipMemcpyDeviceToHost, s), "read optics xi err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");
+    if (int rc = ecc::read_dev_words(ctx, ctx->dev->optics_xi, 2, f, ecc::as_stream(stream))) return rc;
     return (f[0] | f[1]) ? ECC_ERR_CAPACITY : ECC_OK;
 }
 

@@ -31,7 +31,6 @@ namespace {
 
 using ecc::rgrid::Grid;
 using ecc::rgrid::kThreads;
-constexpr int kFlagWord = 6;  // ctx->flags[6]: bit 1 list capacity exceeded
 
 // One lane per point in cell order.  K = 0: counts only; otherwise the K smallest d^2 (K >=
 // min_pts).  kLists: write the neighbour indices at offsets[i].
@@ -193,7 +192,7 @@ int radius_query(ecc_ctx *ctx, const ecc::rgrid::Ws &w, int64_t n, double eps, i
         ECC_TIMED(ctx, s, nbr ? "radius_lists_kernel" : "radius_counts_kernel");
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(kThreads), 0, s, (const Grid *)w.grid, n, (const int32_t *)w.sidx, sc,
                            (const int64_t *)w.cell_off, eps2, min_pts, counts, select ? nullptr : core, offsets, nbr,
-                           nbr_dist, nbr_cap, ctx->flags + kFlagWord);
+                           nbr_dist, nbr_cap, &ctx->dev->radius[0]);
     }
     ECC_CHECK_LAUNCH(ctx, "radius_query_kernel");
     if (select) {
@@ -255,7 +254,7 @@ int radius_lists(ecc_ctx *ctx, const T *pts, int64_t n, int32_t dim, double eps,
     if (n == 0) return ECC_OK;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(ctx->flags + kFlagWord, 0, 4, s), "memset(radius err)");
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(&ctx->dev->radius[0], 0, 4, s), "memset(radius err)");
     if (!nbr) {  // size query: the offsets only (offsets[n] = entries needed)
         rc = ecc::ws_reserve(ctx, ecc::scan_scratch_bytes(n));
         if (rc) return rc;
@@ -296,10 +295,8 @@ ECC_API int ecc_radius_lists_f32(ecc_ctx *ctx, const float *pts, int64_t n, int3
 ECC_API int ecc_radius_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (!ctx) return ECC_ERR_INVALID;
     int32_t f[2] = {0, 0};
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(f, ctx->flags + kFlagWord, 8, hipMemcpyDeviceToHost, ecc::as_stream(stream)),
-                  "read radius err");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(ecc::as_stream(stream)), "sync");
-    if (f[1]) return ECC_ERR_INVALID;  // flags[7]: a non-finite coordinate
+    if (int rc = ecc::read_dev_words(ctx, ctx->dev->radius, 2, f, ecc::as_stream(stream))) return rc;
+    if (f[1]) return ECC_ERR_INVALID;  // a non-finite coordinate (the grid build)
     return f[0] ? ECC_ERR_CAPACITY : ECC_OK;
 }
 

@@ -29,8 +29,6 @@ namespace ecc {
 namespace rgrid {
 
 constexpr int kThreads = 256;
-constexpr int kGridWord = 16;  // ctx->flags[16..]: bounding-box keys, then the grid geometry
-constexpr int kBadWord = 7;    // ctx->flags[7]: bit 1 = a non-finite coordinate was seen (radius status)
 
 // order-preserving int64 key of a double (and back)
 __device__ __forceinline__ int64_t dkey(double v) {
@@ -193,9 +191,9 @@ int build(ecc_ctx *ctx, const T *pts, int64_t n, int dim, double eps, hipStream_
     w.cell_of = reinterpret_cast<int32_t *>(carve((size_t)n * 4));
     w.sidx = reinterpret_cast<int32_t *>(carve((size_t)n * 4));
     w.sc = carve((size_t)n * sizeof(T) * dim);
-    w.keys = reinterpret_cast<int64_t *>(ctx->flags + kGridWord);
-    w.grid = reinterpret_cast<Grid *>(ctx->flags + kGridWord + 12);
-    int32_t *bad = ctx->flags + kBadWord;
+    w.keys = ctx->dev->box_keys;
+    w.grid = &ctx->dev->grid;
+    int32_t *bad = &ctx->dev->radius[1];  // bit 1: a non-finite coordinate was seen (ecc_radius_status)
     const unsigned blocks = (unsigned)std::min<int64_t>((n + kThreads - 1) / kThreads, 4096);
     ECC_CHECK_HIP(ctx, hipMemsetAsync(bad, 0, 4, s), "memset(radius bad)");
     hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(kThreads), 0, s, w.keys);
@@ -219,14 +217,6 @@ int build(ecc_ctx *ctx, const T *pts, int64_t n, int dim, double eps, hipStream_
     }
     ECC_CHECK_LAUNCH(ctx, "radius grid");
     return ECC_OK;
-}
-
-// status word of the last build: a non-finite coordinate -> ECC_ERR_INVALID
-inline int bad_status(ecc_ctx *ctx, hipStream_t s) {
-    int32_t f = 0;
-    ECC_CHECK_HIP(ctx, hipMemcpyAsync(&f, ctx->flags + kBadWord, 4, hipMemcpyDeviceToHost, s), "read radius bad");
-    ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");
-    return f ? ECC_ERR_INVALID : ECC_OK;
 }
 
 }  // namespace rgrid

@@ -1640,6 +1640,82 @@ def test_dbscan_extract_rejects_out_of_segment_neighbours(ecc, gpu):
     assert int(d_nc.numpy()[0]) == 1 and (d_lab.numpy()[:m] == 0).all()  # one ring of 40 core points
 
 
+def _windows_pipeline_bytes(ecc, gpu, xy, n_segs, stride, counts, eps, min_pts):
+    """Every per-window entry point on one set of segments; {name: bytes} of what each wrote.  The
+    output buffers start from a fixed pattern, so slots a kernel leaves alone compare equal too."""
+    n = n_segs * stride
+    d_xy, d_u = dev(ecc, xy), dev(ecc, counts)
+
+    def out(count, dtype):
+        return dev(ecc, np.full(count, 0x5A, np.uint8).repeat(np.dtype(dtype).itemsize).view(dtype))
+
+    def dbscan_outputs():
+        dup_cap = 1 << 16
+        return out(n, np.int32), out(n_segs, np.int32), out(2 * dup_cap, np.int64), dup_cap, out(1, np.int64)
+
+    def dbscan_bytes(d_lab, d_nc, d_dups, d_nd):
+        assert gpu.dbscan_status() == ecc.OK, gpu.last_error()
+        nd = int(d_nd.numpy()[0])
+        pairs = d_dups.numpy()[:2 * nd].reshape(-1, 2)
+        # duplicate memberships are appended through a device-wide counter: any order, so sorted
+        pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]
+        return d_lab.numpy().tobytes() + d_nc.numpy().tobytes() + np.int64(nd).tobytes() + pairs.tobytes()
+
+    res = {}
+    d_cnt = out(n, np.int32)
+    gpu.eps_counts(d_xy, n_segs, stride, d_u, eps, 1, d_cnt, None)
+    gpu.sync()
+    cnt = d_cnt.numpy()
+    res["eps_counts"] = cnt.tobytes()
+    cap = int(cnt.clip(0).sum()) + 16
+    d_off, d_nbr = out(n + 1, np.int64), out(cap, np.int32)
+    gpu.eps_lists(d_xy, n_segs, stride, d_u, eps, d_cnt, d_off, d_nbr, cap)
+    total = C.c_int64(0)
+    assert ecc.lib.ecc_eps_total(gpu.ctx, d_off.ptr, n, C.byref(total), gpu.stream) == ecc.OK
+    assert total.value <= cap
+    d_lab, d_nc, d_dups, dup_cap, d_nd = dbscan_outputs()
+    gpu.dbscan_extract(n_segs, stride, d_u, d_off, d_nbr, min_pts, 1, 1 << 30, d_lab, d_nc, d_dups, dup_cap, d_nd)
+    res["eps_lists + dbscan_extract"] = (d_off.numpy().tobytes() + d_nbr.numpy().tobytes() +
+                                         dbscan_bytes(d_lab, d_nc, d_dups, d_nd))
+    d_lab, d_nc, d_dups, dup_cap, d_nd = dbscan_outputs()
+    gpu.dbscan_grid(d_xy, n_segs, stride, d_u, eps, min_pts, 1, 1 << 30, d_lab, d_nc, d_dups, dup_cap, d_nd)
+    res["dbscan_grid"] = dbscan_bytes(d_lab, d_nc, d_dups, d_nd)
+    d_order, d_reach = out(n, np.int32), out(n, np.float64)
+    d_cl, d_ncl = out(n, np.int32), out(n_segs, np.int32)
+    gpu.optics_grid(d_xy, n_segs, stride, d_u, eps, min_pts, eps, d_order, d_reach, d_cl, d_ncl)
+    assert gpu.optics_grid_status() == ecc.OK
+    res["optics_grid"] = b"".join(a.numpy().tobytes() for a in (d_order, d_reach, d_cl, d_ncl))
+    xi_cap = 64
+    d_pairs, d_np = out(n_segs * xi_cap * 2, np.int32), out(n_segs, np.int32)
+    gpu.optics_xi(d_reach, n_segs, stride, d_u, 0.1, min_pts, 0.0, d_pairs, xi_cap, d_np)
+    assert gpu.optics_xi_status() == ecc.OK
+    res["optics_xi"] = d_pairs.numpy().tobytes() + d_np.numpy().tobytes()
+    st_cap = stride
+    d_stats, d_nst = out(n_segs * st_cap, ecc.CLUSTER_STAT_DTYPE), out(n_segs, np.int32)
+    gpu.cluster_stats_runs(d_xy, d_order, d_cl, n_segs, stride, d_u, d_stats, st_cap, d_nst)
+    assert gpu.cluster_stats_status() == ecc.OK
+    res["cluster_stats_runs"] = d_stats.numpy().tobytes() + d_nst.numpy().tobytes()
+    return res
+
+
+def test_segment_counts_are_clamped_everywhere(ecc, gpu):
+    """A segment count below 0 is an empty segment and one above the stride is the stride, at every
+    entry point that takes windows: counts [100, -5, stride + 7, 100] give the bytes of
+    [100, 0, stride, 100].  (Segment 2's slots past its 100 pixels all hold pixel (0, 0): a segment
+    that repeats a pixel, which the row-run kernels leave to the candidate walks.)"""
+    rng = np.random.default_rng(2024)
+    n_segs, stride = 4, 256
+    xy = np.zeros(n_segs * stride, np.uint32)
+    for s in range(n_segs):
+        cells = rng.choice(20 * 20, 100, replace=False)  # 100 distinct pixels, a quarter of a 20 x 20 patch
+        xy[s * stride: s * stride + 100] = ecc.pack_xy(cells % 20 + 10 * s, cells // 20 + 3)
+    raw = _windows_pipeline_bytes(ecc, gpu, xy, n_segs, stride, np.array([100, -5, stride + 7, 100], np.int32), 2.0, 3)
+    clamped = _windows_pipeline_bytes(ecc, gpu, xy, n_segs, stride, np.array([100, 0, stride, 100], np.int32), 2.0, 3)
+    assert list(raw) == list(clamped)
+    for name in raw:
+        assert raw[name] == clamped[name], name
+
+
 # ------------------------------------------------------------------------------ HIP graph replay
 def test_graph_replay_matches_eager(ecc, orc, gpu):
     """ecc_graph_begin/end/launch: a captured downsample -> k-means -> corners -> NMS step replays
