@@ -1803,15 +1803,8 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
         // > 64 KiB: opt in (gfx950 has 160 KiB); the dedup bitmap only while two workgroups fit a CU
         const size_t lds = ((size_t)nb + kSortSent + kSortChunk + g.dedup_words) * 4;
         constexpr int kLdsCap = (kMaxTiles + 1 + kSortSent + kSortChunk) * 4;
-        static int lds_set[2] = {0, 0};
-        const int bm = g.border_mode == 1 ? 1 : 0;
-        const auto kern = bm ? &slice_sort_kernel<true> : &slice_sort_kernel<false>;
-        if ((int)lds > lds_set[bm]) {
-            ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kLdsCap),
-                          "slice_sort LDS");
-            lds_set[bm] = kLdsCap;
-        }
+        const auto kern = g.border_mode == 1 ? &slice_sort_kernel<true> : &slice_sort_kernel<false>;
+        if ((rc = ecc::allow_dynamic_lds(ctx, kern, kLdsCap, "slice_sort LDS"))) return rc;
         ECC_TIMED(ctx, s, "slice_sort_kernel");
         hipLaunchKernelGGL(kern, dim3((unsigned)g.n_slices), dim3(kSortThreads), lds, s, xy, t, g,
                            so, first_border, &ctx->dev->sort_pending, st->prep_tag,
@@ -1867,14 +1860,8 @@ static int fast_detect_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t
         constexpr size_t kLdsMax = kFlagDynLdsMax;
         const size_t lds = (size_t)g.n_tiles * kSegWords * sizeof(uint32_t);
         if (lds <= kLdsMax) {
-            static bool lds_set[2] = {false, false};
-            const void *fn = cand ? reinterpret_cast<const void *>(&flags_event_kernel<true, true>)
-                                  : reinterpret_cast<const void *>(&flags_event_kernel<true, false>);
-            if (lds > 65536 && !lds_set[cand ? 1 : 0]) {
-                ECC_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax),
-                              "flags LDS");
-                lds_set[cand ? 1 : 0] = true;
-            }
+            const auto fn = cand ? &flags_event_kernel<true, true> : &flags_event_kernel<true, false>;
+            if (lds > 65536 && (rc = ecc::allow_dynamic_lds(ctx, fn, (int)kLdsMax, "flags LDS"))) return rc;
             if (cand)
                 hipLaunchKernelGGL((flags_event_kernel<true, true>), dim3((unsigned)g.n_slices), dim3(kFlagThreads), lds, s,
                                    xy, g, (const uint32_t *)gi.res, (const int32_t *)first_border, corner_flags, cand,

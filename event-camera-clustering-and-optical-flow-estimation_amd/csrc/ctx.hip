@@ -36,6 +36,16 @@ int ws_reserve(ecc_ctx *ctx, size_t bytes) {
     return ECC_OK;
 }
 
+int allow_dynamic_lds(ecc_ctx *ctx, const void *kernel, int bytes, const char *what) {
+    auto it = ctx->lds_grants.begin();
+    while (it != ctx->lds_grants.end() && it->first != kernel) ++it;
+    if (it != ctx->lds_grants.end() && bytes <= it->second) return ECC_OK;
+    ECC_CHECK_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
+    if (it != ctx->lds_grants.end()) it->second = bytes;
+    else ctx->lds_grants.emplace_back(kernel, bytes);
+    return ECC_OK;
+}
+
 int read_dev_words(ecc_ctx *ctx, const int32_t *src, int n, int32_t *out, hipStream_t s) {
     ECC_CHECK_HIP(ctx, hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToHost, s), "read device words");
     ECC_CHECK_HIP(ctx, hipStreamSynchronize(s), "sync");

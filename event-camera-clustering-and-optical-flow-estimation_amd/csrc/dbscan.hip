@@ -1156,9 +1156,7 @@ ECC_API int ecc_dbscan_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, in
     const int r2i = (int)std::floor(eps * eps), e_int = (int)std::floor(eps);
     const size_t lds = (size_t)(ecc::epsg::kCells + 1 + seg_stride) * 4 + (size_t)((seg_stride + 1) & ~1ll) * 2 +
                        (size_t)seg_stride * 4;
-    ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(dbscan_grid_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                  "dbscan_grid lds");
+    if (int rc = ecc::allow_dynamic_lds(ctx, dbscan_grid_kernel, (int)lds, "dbscan_grid lds")) return rc;
     // the row-run kernel first (distinct-pixel segments whose bitmap fits its LDS); the grid kernel
     // takes what it leaves, and exits at once when it leaves nothing
     const bool run = e_int < kDrHw && !getenv_flag("ECC_DBSCAN_GRID_ONLY");

@@ -43,6 +43,8 @@ struct ecc_ctx {
     size_t ws_bytes = 0;
     // The kernels' status words and small device-side results (ecc::DevWords below).
     ecc::DevWords *dev = nullptr;
+    // Largest dynamic-LDS grant made per kernel on this context's device (ecc::allow_dynamic_lds).
+    std::vector<std::pair<const void *, int>> lds_grants;
 };
 
 namespace ecc {
@@ -55,7 +57,7 @@ struct DevWords {
     int32_t eps_lists;         // eps.hip: the lists disagree with the counts, or nbr_cap exceeded
     int32_t evt;               // evt.hip: bit 1 capacity, bit 2 unsorted t
     int32_t dbscan;            // dbscan.hip: bit 1 capacity, bit 2 a neighbour index outside its segment
-    int32_t kmeans_frame;      // kmeans.hip: a point outside the count frame
+    int32_t kmeans_frame;      // kmeans_xy16.hip: a point outside the count frame
     int32_t radius[2];         // radius.hip: [0] bit 1 list capacity; radius_grid.hpp: [1] non-finite input
     int32_t dbscan_cloud;      // dbscan_cloud.hip: bit 1 duplicate capacity
     int32_t eps_left;          // eps.hip: segments the row-run counts left to the candidate walk
@@ -89,6 +91,15 @@ int hip_fail(ecc_ctx *ctx, hipError_t e, const char *what);
 
 // Ensures the context workspace holds >= bytes (16-byte aligned carve base). Returns status.
 int ws_reserve(ecc_ctx *ctx, size_t bytes);
+
+// Lets `kernel` be launched with up to `bytes` of dynamic LDS on the context's device (which must
+// be current).  The runtime keeps the attribute per device, so the context remembers its own
+// largest grant per kernel and calls the runtime only to raise it.  Returns status.
+int allow_dynamic_lds(ecc_ctx *ctx, const void *kernel, int bytes, const char *what);
+template <class... A>
+int allow_dynamic_lds(ecc_ctx *ctx, void (*kernel)(A...), int bytes, const char *what) {
+    return allow_dynamic_lds(ctx, reinterpret_cast<const void *>(kernel), bytes, what);
+}
 
 inline hipStream_t as_stream(ecc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -424,9 +424,7 @@ ECC_API int ecc_eps_counts(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int
     const Kern kern = stage ? (Kern)ECC_EPS_PICK(true) : (Kern)ECC_EPS_PICK(false);
 #undef ECC_EPS_PICK
     const size_t lds = grid_lds + (stage ? stage_lds : 0);
-    ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                  "eps_counts lds");
+    if ((rc = ecc::allow_dynamic_lds(ctx, kern, (int)lds, "eps_counts lds"))) return rc;
     hipStream_t s = ecc::as_stream(stream);
     // counts: the row-run kernel (eps < 512); with core distances when min_pts <= 8 and eps < 32.
     // Its leftovers (segments that repeat a pixel or whose bitmap exceeds its LDS) go through the
@@ -481,9 +479,7 @@ ECC_API int ecc_eps_lists(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int6
     const int r2i = (int)std::floor(eps * eps), e_int = (int)std::floor(eps);
     const size_t grid_words = (size_t)((kCells + 1 + seg_stride + (seg_stride + 1) / 2 + 1) & ~1ll);
     const size_t lds = grid_words * 4 + (size_t)(kNT / 64) * ((seg_stride + 63) / 64) * 8;
-    ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(eps_lists_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                  "eps_lists lds");
+    if ((rc = ecc::allow_dynamic_lds(ctx, eps_lists_kernel, (int)lds, "eps_lists lds"))) return rc;
     const unsigned grid = (unsigned)std::min<int64_t>(n_segs, 2048);
     {
         ECC_TIMED(ctx, s, "eps_lists_kernel");

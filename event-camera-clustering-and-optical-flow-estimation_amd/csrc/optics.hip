@@ -299,9 +299,7 @@ ECC_API int ecc_optics_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, in
     static_assert((kCells + 1 + 3 * kMaxPts + 2 * (kMaxPts / 32)) * 4 + kMaxPts * 4 + 64 * 4 + (kNT / 64) * 4 <=
                       160 * 1024,
                   "LDS of optics_grid_kernel at the largest stride");
-    ECC_CHECK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                  "optics_grid lds");
+    if (int rc = ecc::allow_dynamic_lds(ctx, kern, (int)lds, "optics_grid lds")) return rc;
     // one workgroup per segment; beyond 4096 the segments are grid-strided
     const unsigned grid = (unsigned)std::min<int64_t>(n_segs, 4096);
     ECC_TIMED(ctx, s, "optics_grid_kernel");
