@@ -6,9 +6,14 @@
 // --chi X [--steep-min-diff Y]: additionally get_chi_clusters_flat(reach, X, min_pts, Y)
 // (optics.hpp:803-944), printed as "xi_clusters K" and one "begin end" line per pair after the
 // existing output; on the host by default, with --device-order from the reach left on the device.
+// --chi-tree (with --chi): after the pairs, get_chi_clusters' forest (optics.hpp:948-995, :1018-1021)
+// as "xi_tree K roots R" and one "level begin end" line per node, depth first; on the host by
+// default, with --device-order from ecc_optics_xi_tree on the pairs left on the device.
 // --stats: after all that, "stats_clusters K" and one "begin size cx cy vx vy" line (%.17g) per
-// threshold cluster and, with --chi, "stats_xi K" and one such line per pair; with --device-order
-// these and the "cluster ..." lines come from ecc_cluster_stats_runs / _pairs on the device.
+// threshold cluster and, with --chi, "stats_xi K" and one such line per pair and, with --chi-tree,
+// "stats_xi_tree K" and one such line per pair in the tree's placed order (children before
+// parents); with --device-order these and the "cluster ..." lines come from
+// ecc_cluster_stats_runs / _pairs on the device.
 #include <algorithm>
 #include <cmath>
 
@@ -35,8 +40,9 @@ using Stats = std::vector<ecc::optics::cluster_stat<2>>;
 struct DeviceOrder {
     std::vector<ecc::optics::reachability_dist> reach;
     bool stats_exact = false;
-    Stats clusters, xi_stats;
+    Stats clusters, xi_stats, xi_tree_stats;
     XiPairs xi;
+    std::vector<ecc::optics::cluster_tree> xi_trees;
 };
 
 static void check(int rc, const char *what) {
@@ -44,7 +50,7 @@ static void check(int rc, const char *what) {
 }
 
 static DeviceOrder device_order(const std::vector<std::array<int, 2>> &pts, size_t min_pts, double eps, double thr,
-                                bool with_xi, double chi, double steep_min_diff) {
+                                bool with_xi, double chi, double steep_min_diff, bool with_tree) {
     DeviceOrder out;
     if (pts.empty()) return out;
     if (pts.size() > 8192) {
@@ -101,6 +107,21 @@ static DeviceOrder device_order(const std::vector<std::array<int, 2>> &pts, size
             out.xi_stats = ecc::optics::cluster_statistics_windows(ctx, d_xy.as<uint32_t>(), d_order.as<int32_t>(),
                                                                    d_pairs.as<int32_t>(), cap, d_np.as<int32_t>(), 1, n,
                                                                    nullptr)[0];
+            if (with_tree) {
+                out.xi_trees = ecc::optics::get_chi_clusters_windows(ctx, d_reach.as<double>(), 1, n, nullptr, chi,
+                                                                     min_pts, steep_min_diff)[0];
+                // the statistics in the placed order: `sorted` as ecc_cluster_stats_pairs' pairs
+                const size_t slots = (size_t)std::max<int64_t>(cap, 1);
+                ecc::DeviceBuffer d_sorted(slots * 8), d_parent(slots * 4), d_roots(4);
+                check(ecc_optics_xi_tree(ctx.get(), d_pairs.as<int32_t>(), cap, d_np.as<int32_t>(), 1,
+                                         d_sorted.as<int32_t>(), d_parent.as<int32_t>(), nullptr,
+                                         d_roots.as<int32_t>(), ctx.stream()),
+                      "ecc_optics_xi_tree");
+                check(ecc_optics_xi_tree_status(ctx.get(), ctx.stream()), "ecc_optics_xi_tree");
+                out.xi_tree_stats = ecc::optics::cluster_statistics_windows(ctx, d_xy.as<uint32_t>(), d_order.as<int32_t>(),
+                                                                            d_sorted.as<int32_t>(), cap, d_np.as<int32_t>(),
+                                                                            1, n, nullptr)[0];
+            }
             break;
         }
     }
@@ -118,6 +139,23 @@ static void print_stats(const char *title, const Stats &stats) {
     for (const auto &c : stats)
         std::printf("%zu %zu %.17g %.17g %.17g %.17g\n", c.begin, c.size, c.centroid[0], c.centroid[1], c.variance[0],
                     c.variance[1]);
+}
+
+static void print_node(const ecc::optics::Node<ecc::optics::chi_cluster_indices> &node, size_t level) {
+    std::printf("%zu %zu %zu\n", level, node.get_data().first, node.get_data().second);
+    for (const auto &c : node.get_children()) print_node(c, level + 1);
+}
+
+// the placed ("sorted") list of flat_clusters_to_tree (ecc_optics_xi_tree_host)
+static XiPairs placed_order(const XiPairs &xi) {
+    std::vector<int32_t> pairs(xi.size() * 2), sorted(xi.size() * 2), parent(xi.size());
+    for (size_t k = 0; k < xi.size(); ++k) pairs[2 * k] = (int32_t)xi[k].first, pairs[2 * k + 1] = (int32_t)xi[k].second;
+    int64_t n_roots = 0;
+    check(ecc_optics_xi_tree_host(pairs.data(), (int64_t)xi.size(), sorted.data(), parent.data(), nullptr, &n_roots),
+          "ecc_optics_xi_tree_host");
+    XiPairs out;
+    for (size_t k = 0; k < xi.size(); ++k) out.emplace_back((size_t)sorted[2 * k], (size_t)sorted[2 * k + 1]);
+    return out;
 }
 
 int main(int argc, char **argv) {
@@ -138,8 +176,13 @@ int main(int argc, char **argv) {
         const bool with_stats = has_flag(argc, argv, "--stats");
         const double chi = opt_double(argc, argv, "--chi", 0.0);
         const double steep_min_diff = opt_double(argc, argv, "--steep-min-diff", 0.0);
+        const bool with_tree = has_flag(argc, argv, "--chi-tree");
+        if (with_tree && !with_xi) {
+            std::fprintf(stderr, "--chi-tree needs --chi X\n");
+            return 1;
+        }
         DeviceOrder dev;
-        if (on_device) dev = device_order(pts, min_pts, eps, thr, with_xi, chi, steep_min_diff);
+        if (on_device) dev = device_order(pts, min_pts, eps, thr, with_xi, chi, steep_min_diff, with_tree);
         const bool from_device = on_device && !pts.empty();
         const auto reach = from_device ? dev.reach : ecc::optics::compute_reachability_dists(pts, min_pts, eps);
         const XiPairs xi = !with_xi      ? XiPairs{}
@@ -159,11 +202,21 @@ int main(int argc, char **argv) {
             std::printf("xi_clusters %zu\n", xi.size());
             for (const auto &c : xi) std::printf("%zu %zu\n", c.first, c.second);
         }
+        if (with_tree) {
+            const auto trees = from_device ? dev.xi_trees
+                                           : ecc::optics::get_chi_clusters(reach, chi, min_pts, steep_min_diff);
+            std::printf("xi_tree %zu roots %zu\n", xi.size(), trees.size());
+            for (const auto &t : trees) print_node(t.get_root(), 0);
+        }
         if (with_stats) {
             print_stats("stats_clusters", clusters);
             if (with_xi)
                 print_stats("stats_xi", from_device && dev.stats_exact ? dev.xi_stats
                                                                        : ecc::optics::cluster_statistics(pts, reach, xi));
+            if (with_tree)
+                print_stats("stats_xi_tree", from_device && dev.stats_exact
+                                                 ? dev.xi_tree_stats
+                                                 : ecc::optics::cluster_statistics(pts, reach, placed_order(xi)));
         }
     } catch (const ecc::Error &e) {
         std::fprintf(stderr, "%s\n", e.what());

@@ -65,6 +65,7 @@ struct DevWords {
     int32_t dbscan_left;       // dbscan.hip: segments dbscan_run_kernel left to dbscan_grid_kernel
     int32_t optics_xi[2];      // optics_xi.hip: [0] more pairs than cap, [1] the workspace check fired
     int32_t cluster_stats[2];  // cluster_stats.hip: [0] more runs than cap, [1] invalid order entry or pair
+    int32_t optics_xi_tree;    // optics_xi_tree.hip: a segment with more pairs than pair_cap
     int64_t box_keys[6];       // radius_grid.hpp: bounding-box keys (3 min, 3 max)
     rgrid::Grid grid;          // radius_grid.hpp: the cloud grid's geometry
 };

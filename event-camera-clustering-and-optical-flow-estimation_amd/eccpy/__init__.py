@@ -209,6 +209,9 @@ _sigs = {
     "ecc_optics_xi_status": (C.c_int, [P, P]),
     "ecc_optics_xi_resident_segments": (C.c_int, [P, P]),
     "ecc_optics_xi_host": (C.c_int, [P, i64, C.c_double, i32, C.c_double, P, i64, P]),
+    "ecc_optics_xi_tree": (C.c_int, [P, P, i64, P, i64, P, P, P, P, P]),
+    "ecc_optics_xi_tree_status": (C.c_int, [P, P]),
+    "ecc_optics_xi_tree_host": (C.c_int, [P, i64, P, P, P, P]),
     "ecc_cluster_stats_runs": (C.c_int, [P, P, P, P, i64, i64, P, P, i64, P, P]),
     "ecc_cluster_stats_pairs": (C.c_int, [P, P, P, P, i64, P, i64, i64, P, P, P]),
     "ecc_cluster_stats_status": (C.c_int, [P, P]),
@@ -559,6 +562,19 @@ class Context:
         check(lib.ecc_optics_xi_resident_segments(self.ctx, C.addressof(v)), "ecc_optics_xi_resident_segments")
         return v.value
 
+    def optics_xi_tree(self, pairs: DeviceArray, pair_cap: int, n_pairs: DeviceArray, n_segs: int,
+                       sorted_pairs: DeviceArray, parent: DeviceArray, level: DeviceArray | None,
+                       n_roots: DeviceArray):
+        """The hierarchy of optics_xi's pairs (pairs, pair_cap, n_pairs as its clusters, cap, n_clusters) of
+        every segment in one launch: sorted_pairs int32[n_segs * pair_cap * 2] (children before parents),
+        parent / level int32[n_segs * pair_cap] (placed positions, -1 = root; level optional), n_roots
+        int32[n_segs] (-1 for a segment with more pairs than pair_cap)."""
+        check(lib.ecc_optics_xi_tree(self.ctx, pairs.ptr, pair_cap, n_pairs.ptr, n_segs, sorted_pairs.ptr, parent.ptr,
+                                     _ptr(level), n_roots.ptr, self.stream), "ecc_optics_xi_tree")
+
+    def optics_xi_tree_status(self) -> int:
+        return lib.ecc_optics_xi_tree_status(self.ctx, self.stream)
+
     def cluster_stats_runs(self, xy: DeviceArray, order: DeviceArray, cluster: DeviceArray, n_segs: int, stride: int,
                            counts_in, stats: DeviceArray, cap: int, n_stats: DeviceArray):
         """Size, centroid and variance of every threshold cluster (maximal run of equal ids in optics_grid's
@@ -797,6 +813,18 @@ def optics_xi_host(reach, chi: float, min_pts: int, steep_area_min_diff: float =
     check(lib.ecc_optics_xi_host(r.ctypes.data, r.size, chi, min_pts, steep_area_min_diff, out.ctypes.data, cap,
                                  C.addressof(n_out)), "ecc_optics_xi_host")
     return out[:n_out.value]
+
+
+def optics_xi_tree_host(pairs):
+    """The hierarchy of one host list of {begin, end} pairs (k, 2) in optics_xi_host's order (no GPU):
+    (sorted int32 (k, 2), parent int32[k], level int32[k], n_roots)."""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    k = len(pairs)
+    out, parent, level = np.zeros((k, 2), np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+    n_roots = C.c_int64(0)
+    check(lib.ecc_optics_xi_tree_host(pairs.ctypes.data, k, out.ctypes.data, parent.ctypes.data, level.ctypes.data,
+                                      C.addressof(n_roots)), "ecc_optics_xi_tree_host")
+    return out, parent, level, n_roots.value
 
 
 def cluster_stats_host(xy, order, pairs):

@@ -9,7 +9,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "../../include/ecc.hpp"
+#include "optics_xi_pairs.hpp"
 
 namespace {
 
@@ -156,23 +156,21 @@ std::vector<std::pair<std::size_t, std::size_t>> get_chi_clusters_flat(const std
     return out;
 }
 
-std::vector<std::vector<std::pair<std::size_t, std::size_t>>> get_chi_clusters_flat_windows(
-    Context &ctx, const double *device_reach, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
-    double chi, std::size_t min_pts, double steep_area_min_diff) {
+int64_t xi_pairs_on_device(Context &ctx, const double *device_reach, int64_t n_segs, int64_t seg_stride,
+                           const int32_t *device_seg_counts, double chi, std::size_t min_pts,
+                           double steep_area_min_diff, DeviceBuffer &d_pairs, DeviceBuffer &d_n,
+                           std::vector<int32_t> &counts) {
     const auto check = [](int rc) {
         if (rc != ECC_OK) throw Error(rc, "ecc_optics_xi");
     };
-    if (n_segs < 0 || min_pts > (std::size_t)INT32_MAX) check(ECC_ERR_INVALID);
-    std::vector<std::vector<std::pair<std::size_t, std::size_t>>> result((size_t)n_segs);
+    if (n_segs < 1 || min_pts > (std::size_t)INT32_MAX) check(ECC_ERR_INVALID);
     ecc_stream_t s = ctx.stream();
-    DeviceBuffer d_n(std::max<size_t>((size_t)n_segs, 1) * 4), d_pairs;
-    std::vector<int32_t> counts((size_t)n_segs), pairs;
-    // a second pass with the largest count as capacity when the first guess was too small
+    d_n.reserve((size_t)n_segs * 4);
+    counts.resize((size_t)n_segs);
     for (int64_t cap = 64;;) {
-        d_pairs.reserve(std::max<size_t>((size_t)n_segs * (size_t)cap, 1) * 8);
+        d_pairs.reserve((size_t)n_segs * (size_t)std::max<int64_t>(cap, 1) * 8);
         check(ecc_optics_xi(ctx.get(), device_reach, n_segs, seg_stride, device_seg_counts, chi, (int32_t)min_pts,
                             steep_area_min_diff, d_pairs.as<int32_t>(), cap, d_n.as<int32_t>(), s));
-        if (n_segs == 0) return result;
         d_n.download(counts.data(), (size_t)n_segs * 4, s);
         const int rc = ecc_optics_xi_status(ctx.get(), s);
         if (rc == ECC_ERR_CAPACITY) {
@@ -182,15 +180,35 @@ std::vector<std::vector<std::pair<std::size_t, std::size_t>>> get_chi_clusters_f
             continue;
         }
         check(rc);
-        pairs.resize((size_t)n_segs * (size_t)cap * 2);
-        d_pairs.download(pairs.data(), pairs.size() * 4, s);
-        ctx.sync();
-        for (int64_t g = 0; g < n_segs; ++g)
-            for (int64_t k = 0; k < counts[(size_t)g]; ++k)
-                result[(size_t)g].emplace_back((std::size_t)pairs[(size_t)((g * cap + k) * 2)],
-                                               (std::size_t)pairs[(size_t)((g * cap + k) * 2 + 1)]);
+        return cap;
+    }
+}
+
+std::vector<std::vector<std::pair<std::size_t, std::size_t>>> get_chi_clusters_flat_windows(
+    Context &ctx, const double *device_reach, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
+    double chi, std::size_t min_pts, double steep_area_min_diff) {
+    if (n_segs < 0) throw Error(ECC_ERR_INVALID, "ecc_optics_xi");
+    std::vector<std::vector<std::pair<std::size_t, std::size_t>>> result((size_t)n_segs);
+    if (n_segs == 0) {  // the parameter checks alone
+        const int rc = min_pts > (std::size_t)INT32_MAX
+                           ? ECC_ERR_INVALID
+                           : ecc_optics_xi(ctx.get(), device_reach, 0, seg_stride, device_seg_counts, chi,
+                                           (int32_t)min_pts, steep_area_min_diff, nullptr, 0, nullptr, ctx.stream());
+        if (rc != ECC_OK) throw Error(rc, "ecc_optics_xi");
         return result;
     }
+    DeviceBuffer d_n, d_pairs;
+    std::vector<int32_t> counts, pairs;
+    const int64_t cap = xi_pairs_on_device(ctx, device_reach, n_segs, seg_stride, device_seg_counts, chi, min_pts,
+                                           steep_area_min_diff, d_pairs, d_n, counts);
+    pairs.resize((size_t)n_segs * (size_t)cap * 2);
+    d_pairs.download(pairs.data(), pairs.size() * 4, ctx.stream());
+    ctx.sync();
+    for (int64_t g = 0; g < n_segs; ++g)
+        for (int64_t k = 0; k < counts[(size_t)g]; ++k)
+            result[(size_t)g].emplace_back((std::size_t)pairs[(size_t)((g * cap + k) * 2)],
+                                           (std::size_t)pairs[(size_t)((g * cap + k) * 2 + 1)]);
+    return result;
 }
 
 }  // namespace optics

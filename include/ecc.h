@@ -612,6 +612,41 @@ int ecc_optics_xi_resident_segments(ecc_ctx *ctx, int32_t *per_cu);
 int ecc_optics_xi_host(const double *reach, int64_t n, double chi, int32_t min_pts,
                        double steep_area_min_diff, int32_t *clusters, int64_t cap, int64_t *n_out);
 
+/* ecc_optics_xi_tree: the hierarchy of every segment's xi pairs, in one launch (a workgroup per
+ * segment; LDS does not grow with pair_cap): what optics::get_chi_clusters returns, as arrays.
+ * Reference: optics::flat_clusters_to_tree OPT/include/optics/optics.hpp:948-995 — the placement
+ *   loop :950-966 (children before parents; NOT a sort by `second`) and the first-parent search
+ *   :974-992 — called by optics::get_chi_clusters :1018-1021 on get_chi_clusters_flat's list.
+ * pairs, n_pairs, pair_cap: DEVICE, exactly ecc_optics_xi's clusters, n_clusters and cap.
+ * Outputs (DEVICE) for segment s with P = n_pairs[s], 0 <= P <= pair_cap (a negative count is 0):
+ *   sorted[(s*pair_cap + k)*2 .. +1] = the pair at placed position k < P;
+ *   parent[s*pair_cap + k] = the placed position of its parent — the first j > k with
+ *                            sorted[k].first >= sorted[j].first && sorted[k].second <= sorted[j].second
+ *                            (an identical later pair is a parent) — or -1 for a root;
+ *   level[s*pair_cap + k]  = 0 for a root, else level[parent] + 1 (level may be NULL);
+ *   n_roots[s]             = the number of roots.
+ *   Roots in ascending k are the reference's result vector, a node's children in ascending k its
+ *   child list, so (sorted, parent) determine the forest.  Entries k >= P are left untouched.
+ * A segment with n_pairs[s] > pair_cap (a truncated flat list) gets n_roots[s] = -1 and nothing
+ * else; other segments are unaffected.  Pair values are compared and never used as an index: pairs
+ * with begin > end, negative values and repeats give what the reference's loops give.  The outputs
+ * must not overlap the inputs.
+ * ECC_ERR_INVALID (before any launch): NULL ctx; NULL pairs / n_pairs / sorted / parent / n_roots
+ * with n_segs > 0; n_segs < 0; pair_cap < 0.  n_segs == 0: ECC_OK after the same range checks.
+ * ecc_optics_xi_tree_status (optics.hpp:948-995): synchronises `stream`; ECC_ERR_CAPACITY if a
+ * segment of the last call had n_pairs[s] > pair_cap; ECC_ERR_INVALID for NULL ctx. */
+int ecc_optics_xi_tree(ecc_ctx *ctx, const int32_t *pairs, int64_t pair_cap, const int32_t *n_pairs,
+                       int64_t n_segs, int32_t *sorted, int32_t *parent, int32_t *level,
+                       int32_t *n_roots, ecc_stream_t stream);
+int ecc_optics_xi_tree_status(ecc_ctx *ctx, ecc_stream_t stream);
+/* ecc_optics_xi_tree_host (optics.hpp:948-995): the same two loops, literally, for ONE list in HOST
+ * memory of any n_pairs <= INT32_MAX, on the host (no GPU, no context): the route for a single
+ * ecc_optics_f64 / ecc_optics_xi_host result.  sorted: HOST int32[n_pairs * 2]; parent, level: HOST
+ * int32[n_pairs] (level may be NULL); *n_roots = the number of roots.  ECC_ERR_INVALID: n_pairs < 0
+ * or above INT32_MAX, NULL n_roots, NULL pairs / sorted / parent with n_pairs > 0. */
+int ecc_optics_xi_tree_host(const int32_t *pairs, int64_t n_pairs, int32_t *sorted, int32_t *parent,
+                            int32_t *level, int64_t *n_roots);
+
 /* ecc_cluster_stats_*: size, centroid and per-axis variance of every cluster of every segment, in
  * one launch (one workgroup per segment), on the arrays ecc_optics_grid / ecc_optics_xi leave on the
  * device: the product line "j,size,cx,cy,devx,devy" of the reference's OPTICS event driver.

@@ -13,6 +13,8 @@
 //                                    OPT/include/optics/optics.hpp:413-565  ecc::optics::compute_reachability_dists
 //                                                                  (runtime N instead of the template N)
 //   optics::get_chi_clusters_flat    optics.hpp:803-944             ecc::optics::get_chi_clusters_flat[_windows]
+//   optics::get_chi_clusters / flat_clusters_to_tree, Node / Tree / tree_depth / tree_size / flatten_dfs
+//                                    optics.hpp:948-995, 1018-1021, tree.hpp  ecc::optics::get_chi_clusters[_windows] ...
 //   optics::get_cluster_points       optics.hpp:692-721, 760-774    ecc::optics::get_cluster_points
 //   per-cluster size, centroid, variance  OPT/test/cluster_event_data.cpp:472-527
 //                                                                  ecc::optics::cluster_statistics[_windows]
@@ -30,6 +32,7 @@
 // Compute always runs on the GPU through libecc; there is no CPU fallback.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstddef>
 #include <cstdint>
@@ -482,6 +485,81 @@ std::vector<std::vector<cluster_stat<2>>> cluster_statistics_windows(
     Context &ctx, const uint32_t *device_xy, const int32_t *device_order, const int32_t *device_pairs,
     int64_t pair_cap, const int32_t *device_n_pairs, int64_t n_segs, int64_t seg_stride,
     const int32_t *device_seg_counts);
+
+// OPT/include/optics/tree.hpp:11-112 — the value-type tree optics::get_chi_clusters returns: a
+// node owns its data and its children, copies are deep.
+template <typename T>
+class Node {  // tree.hpp:15-54
+  public:
+    Node(T data) : data_(std::move(data)) {}
+    Node(T data, std::vector<Node<T>> children) : data_(std::move(data)), children_(std::move(children)) {}
+    T get_data() const { return data_; }
+    std::vector<Node<T>> &get_children() { return children_; }
+    const std::vector<Node<T>> &get_children() const { return children_; }
+    void add_child(const Node<T> &new_child) { children_.push_back(new_child); }
+    void add_children(const std::vector<Node<T>> &new_children) {
+        children_.insert(children_.end(), new_children.begin(), new_children.end());
+    }
+
+  private:
+    T data_;
+    std::vector<Node<T>> children_;
+};
+
+template <typename T>
+class Tree {  // tree.hpp:57-79
+  public:
+    Tree() : root_(T{}) {}
+    Tree(Node<T> root) : root_(std::move(root)) {}
+    std::vector<T> flatten() const {  // the root, then every subtree in child order
+        std::vector<T> result;
+        preorder(root_, result);
+        return result;
+    }
+    Node<T> &get_root() { return root_; }
+    const Node<T> &get_root() const { return root_; }
+
+  private:
+    static void preorder(const Node<T> &node, std::vector<T> &out) {
+        out.push_back(node.get_data());
+        for (const auto &c : node.get_children()) preorder(c, out);
+    }
+    Node<T> root_;
+};
+
+template <typename T>
+std::size_t tree_depth(const Node<T> &root) {  // tree.hpp:82-87: a leaf has depth 1
+    std::size_t deepest = 0;
+    for (const auto &c : root.get_children()) deepest = std::max(deepest, tree_depth(c));
+    return 1 + deepest;
+}
+template <typename T>
+std::size_t tree_size(const Node<T> &root) {  // tree.hpp:89-93
+    std::size_t n = 1;
+    for (const auto &c : root.get_children()) n += tree_size(c);
+    return n;
+}
+template <typename T>
+std::vector<T> flatten_dfs(const Tree<T> &t) {  // tree.hpp:106-112
+    return t.flatten();
+}
+
+using cluster_tree = Tree<chi_cluster_indices>;  // optics.hpp:51
+
+// optics.hpp:948-995 — the forest of nested clusters of a flat xi list (ecc_optics_xi_tree_host: the
+// reference's placement loop and first-parent search, literally; no GPU).  Trees in the
+// reference's order, children in the order it adds them.  Error(ECC_ERR_INVALID) for a position
+// above INT32_MAX.
+std::vector<cluster_tree> flat_clusters_to_tree(const std::vector<chi_cluster_indices> &clusters_flat);
+// optics.hpp:1018-1021 — flat_clusters_to_tree(get_chi_clusters_flat(...)), both on the host.
+std::vector<cluster_tree> get_chi_clusters(const std::vector<reachability_dist> &reach_dists, double chi,
+                                           std::size_t min_pts, double steep_area_min_diff = 0.0);
+// The same for many plots already on the DEVICE (ecc_optics_xi, then ecc_optics_xi_tree on the pairs
+// it leaves there: one launch each for all segments; arguments as get_chi_clusters_flat_windows).
+// One forest per segment.  Synchronises the context's stream.
+std::vector<std::vector<cluster_tree>> get_chi_clusters_windows(
+    Context &ctx, const double *device_reach, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
+    double chi, std::size_t min_pts, double steep_area_min_diff = 0.0);
 
 }  // namespace optics
 
