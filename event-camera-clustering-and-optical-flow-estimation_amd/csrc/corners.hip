@@ -1465,7 +1465,8 @@ __device__ __forceinline__ uint32_t corner_bit(uint32_t v, const CornerGeom &g, 
 // kCand (ecc_fast_detect_nms): the pass also writes each slice's NMS candidate list — the
 // flagged events' xy in event order at cand[s * S ...], their count in n_cand[s] — which is
 // what nms_compact_kernel would rebuild from the flags (the host takes this form only for
-// slices of at most kFlagCandMax events, a multiple of 4).
+// slices of at most kFlagCandMax events, a multiple of 4, with 4-B aligned flags: every slice then
+// runs in quads).
 // 256-lane workgroups, one per slice, so that all 1221 slices of the bench batch are resident at
 // once (eight per CU; 512-lane ones left a second round of 197 workgroups as a tail).  A slice's
 // quads are taken in batches of kFlagQuads per lane: the first batch's loads are issued before
@@ -1484,7 +1485,9 @@ flags_event_kernel(const uint32_t *__restrict__ xy, CornerGeom g, const uint32_t
     // events [0, live_end) of the slice can be corners
     const int live_end = s < g.first_detect ? 0 : (g.border_mode == 1 ? min(len, max(first_border[s], 0)) : len);
     const uint32_t *rg = res + s * g.seg_stride;  // slice s's segment of every tile (16-B aligned)
-    const bool vec = (lo & 3) == 0;  // 4-event quads: 16-B loads, 4-B flag stores
+    // 4-event quads (16-B loads through the view, which need 4 B; 4-B flag stores, taken by the
+    // store's ADDRESS: the slice's first event plus the flags pointer's own offset)
+    const bool vec = ((lo + (int64_t)(reinterpret_cast<uintptr_t>(flags) & 3)) & 3) == 0;  // uniform
     const int n4 = vec ? len / 4 : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // all loads unconditional through a buffer view of the slice's whole quads (0 past them): a
@@ -1926,8 +1929,10 @@ static int fast_detect_nms_phases(ecc_ctx *ctx, const uint32_t *xy, const int64_
     const int64_t tiles = (int64_t)((cfg->width + kTile - 1) / kTile) * ((cfg->height + kTile - 1) / kTile);
     uint32_t *cand = nullptr;
     int32_t *n_cand = nullptr;
+    // (flags off 4-B alignment: the candidate form would leave each slice to one lane; the flag pass's
+    // all-lane scalar arm and nms_compact_kernel take such callers)
     if (n > 0 && cfg->slice_events % 4 == 0 && cfg->slice_events <= kFlagCandMax &&
-        tiles * kSegWords * 4 <= (int64_t)kFlagDynLdsMax) {
+        (reinterpret_cast<uintptr_t>(corner_flags) & 3) == 0 && tiles * kSegWords * 4 <= (int64_t)kFlagDynLdsMax) {
         int rc = ecc::nms_candidates(ctx, n, cfg->slice_events, cfg->width, cfg->height, box_size, &cand, &n_cand);
         if (rc) return rc;
     }

@@ -40,12 +40,15 @@ dedup_exact_kernel(const uint32_t *__restrict__ xy, int64_t n, int window, int n
     for (int i = tid; i < kSlots; i += kThreads) table[i] = kEmptySlot;
     uint32_t v[kMaxChunks][4];
     int slot[kMaxChunks][4];
+    // 16-B loads where the window's first ADDRESS is 16-B aligned (every lane's quad then is): the
+    // element index plus the pointer's own offset, so xy needs only its type's 4-B alignment
+    const bool quads = ((wbase + (int64_t)(reinterpret_cast<uintptr_t>(xy) >> 2)) & 3) == 0;  // uniform
 #pragma unroll
     for (int c = 0; c < kMaxChunks; ++c) {
         if (c >= n_chunks) continue;
         const int li = c * kChunk + 4 * tid;
         const int64_t g = wbase + li;
-        if (li + 3 < m && (g & 3) == 0) {
+        if (li + 3 < m && quads) {
             const uint4 q = *reinterpret_cast<const uint4 *>(xy + g);
             v[c][0] = q.x; v[c][1] = q.y; v[c][2] = q.z; v[c][3] = q.w;
         } else {

@@ -466,7 +466,10 @@ ECC_API int ecc_eps_lists(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int6
     int rc = check_segs(ctx, xy, n_segs, seg_stride, eps);
     if (rc) return rc;
     if (!counts || !offsets || (nbr_cap > 0 && !nbr) || nbr_cap < 0) return ECC_ERR_INVALID;
-    if (n_segs == 0) return ECC_OK;
+    if (n_segs == 0) {  // the scan of no counts: offsets[0] = 0 (the total ecc_eps_total reads)
+        ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+        return ecc::exclusive_scan_i32_i64(ctx, counts, 0, offsets, nullptr, ecc::as_stream(stream));
+    }
     const int64_t n = n_segs * seg_stride;
     rc = ecc::ws_reserve(ctx, ecc::scan_scratch_bytes(n));
     if (rc) return rc;

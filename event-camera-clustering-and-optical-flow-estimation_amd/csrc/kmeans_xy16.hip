@@ -24,6 +24,12 @@
 
 namespace {
 
+// The labels pointer's own offset, in bytes: packed 4-B label stores are taken where element index
+// plus this is a multiple of 4, so labels needs no alignment at all.
+__device__ __forceinline__ int64_t label_skew(const uint8_t *labels) {
+    return (int64_t)(reinterpret_cast<uintptr_t>(labels) & 3);
+}
+
 template <bool kAccumulate>
 __global__ void __launch_bounds__(kThreads)
 kmeans_xy16_kernel(const uint32_t *__restrict__ xy, Segs segs, const float *__restrict__ cent,
@@ -42,10 +48,13 @@ kmeans_xy16_kernel(const uint32_t *__restrict__ xy, Segs segs, const float *__re
         }
     }
     __syncthreads();
-    const bool vec_ok = (segs.stride & 3) == 0;
+    // vector forms by ADDRESS (element index + the pointer's own offset; both uniform per segment):
+    // 16-B loads of xy, 4-B stores of labels.  Either pointer needs only its type's alignment.
+    const int64_t xy_skew = (int64_t)(reinterpret_cast<uintptr_t>(xy) >> 2), lab_skew = label_skew(labels);
     for (int64_t s = blockIdx.x; s < segs.n_segs; s += gridDim.x) {
         const int64_t cnt = segs.count(s);
         const int64_t base = s * segs.stride;
+        const bool vec_ok = ((base + xy_skew) & 3) == 0, st_ok = ((base + lab_skew) & 3) == 0;
         for (int64_t j = 4 * tid; j < cnt; j += 4 * kThreads) {
             uint32_t v[4];
             if (vec_ok && j + 3 < cnt) {
@@ -67,7 +76,7 @@ kmeans_xy16_kernel(const uint32_t *__restrict__ xy, Segs segs, const float *__re
                 }
             }
             if (labels) {
-                if (j + 3 < cnt && ((base + j) & 3) == 0) {
+                if (j + 3 < cnt && st_ok) {
                     const uint32_t pk = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
                     *reinterpret_cast<uint32_t *>(labels + base + j) = pk;
                 } else {
@@ -133,13 +142,16 @@ kmeans_fast_kernel(const uint32_t *__restrict__ xy, Segs segs, const float *__re
             ty += w & ((1ull << 26) - 1);
         }
     };
+    const int64_t lab_skew = label_skew(labels);
     for (int64_t s = blockIdx.x; s < segs.n_segs; s += gridDim.x) {
         const int64_t cnt = segs.count(s);
         const int64_t base = s * segs.stride;
+        const bool st_ok = ((base + lab_skew) & 3) == 0;  // 4-B label stores by address (uniform)
         // Two 4-point batches per lane per trip: both loads and all eight label gathers are in
         // flight before the first LDS add, halving the dependent load -> gather -> add rounds.
-        // the segment through a buffer view rounded up to 16 B (inside the allocation's last 16-B
-        // block; points past cnt are masked): unconditional 16-B loads (4-B alignment suffices)
+        // the segment through a buffer view rounded up to 16 B (up to 12 B past the last point: the
+        // bytes include/ecc.h asks callers to keep readable; points past cnt are masked):
+        // unconditional 16-B loads (4-B alignment suffices)
         const __amdgpu_buffer_rsrc_t vs = ecc::buffer_view(xy + base, (uint32_t)((cnt * 4 + 15) & ~15ll));
         for (int64_t j0 = 0; j0 < cnt; j0 += 8 * kThreads) {  // uniform trip count per WG
             uint32_t v[8], lab[8];
@@ -188,7 +200,7 @@ kmeans_fast_kernel(const uint32_t *__restrict__ xy, Segs segs, const float *__re
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const int64_t j = j0 + u * 4 * kThreads + 4 * tid;
-                    if (j + 3 < cnt && ((base + j) & 3) == 0) {
+                    if (j + 3 < cnt && st_ok) {
                         const uint32_t pk = lab[4 * u] | (lab[4 * u + 1] << 8) | (lab[4 * u + 2] << 16) |
                                             (lab[4 * u + 3] << 24);
                         *reinterpret_cast<uint32_t *>(labels + base + j) = pk;
@@ -236,8 +248,10 @@ kmeans_img_labels_kernel(const uint32_t *__restrict__ xy, Segs segs, const float
     }
     __syncthreads();
     const uint32_t img_w = img_wh[0], img_h = img_wh[1];
+    const int64_t lab_skew = label_skew(labels);
     for (int64_t s = blockIdx.x; s < segs.n_segs; s += gridDim.x) {
         const int64_t base = s * segs.stride;
+        const bool st_ok = ((base + lab_skew) & 3) == 0;  // 4-B label stores by address (uniform)
         // readable extent: the whole stride (the next segment starts after it), except in the
         // last segment, whose buffer may end at its count
         const int64_t cnt = segs.count(s);
@@ -269,7 +283,7 @@ kmeans_img_labels_kernel(const uint32_t *__restrict__ xy, Segs segs, const float
 #pragma unroll
             for (int u = 0; u < kLabPer / 4; ++u) {
                 const int64_t j = j0 + u * 4 * kThreads + 4 * tid;
-                if (j + 3 < cnt && ((base + j) & 3) == 0) {
+                if (j + 3 < cnt && st_ok) {
                     const uint32_t pk = lab[4 * u] | (lab[4 * u + 1] << 8) | (lab[4 * u + 2] << 16) |
                                         (lab[4 * u + 3] << 24);
                     *reinterpret_cast<uint32_t *>(labels + base + j) = pk;
@@ -319,14 +333,17 @@ kmeans_lds_labels_kernel(const uint32_t *__restrict__ xy, Segs segs, const float
         }
     }
     __syncthreads();
+    const int64_t lab_skew = label_skew(labels);
     for (int64_t s0 = 4 * (int64_t)blockIdx.x; s0 < segs.n_segs; s0 += 4 * (int64_t)gridDim.x) {
         const int64_t s = s0 + sub;
         if (s >= segs.n_segs) continue;  // no barrier below
         const int64_t base = s * segs.stride;
+        const bool st_ok = ((base + lab_skew) & 3) == 0;  // 4-B label stores by address (per sub-group)
         const int64_t cnt = segs.count(s);
         const int64_t lim = s + 1 < segs.n_segs ? segs.stride : cnt;
-        // the segment through a buffer view rounded up to 16 B (inside the allocation's last 16-B
-        // block; points past cnt are masked): one unconditional 16-B load per quad
+        // the segment through a buffer view rounded up to 16 B (up to 12 B past the last point, which
+        // include/ecc.h asks callers to keep readable; points past cnt are masked): one
+        // unconditional 16-B load per quad
         const __amdgpu_buffer_rsrc_t vs = ecc::buffer_view(xy + base, (uint32_t)((lim * 4 + 15) & ~15ll));
         for (int64_t j0 = 0; j0 < cnt; j0 += kLabPer * 256) {
             uint32_t v[kLabPer], lab[kLabPer];
@@ -354,7 +371,7 @@ kmeans_lds_labels_kernel(const uint32_t *__restrict__ xy, Segs segs, const float
 #pragma unroll
             for (int u = 0; u < kLabPer / 4; ++u) {
                 const int64_t j = j0 + u * 4 * 256 + 4 * t;
-                if (j + 3 < cnt && ((base + j) & 3) == 0) {
+                if (j + 3 < cnt && st_ok) {
                     const uint32_t pk = lab[4 * u] | (lab[4 * u + 1] << 8) | (lab[4 * u + 2] << 16) |
                                         (lab[4 * u + 3] << 24);
                     *reinterpret_cast<uint32_t *>(labels + base + j) = pk;

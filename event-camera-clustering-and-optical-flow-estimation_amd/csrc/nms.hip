@@ -63,10 +63,12 @@ nms_kernel(const uint32_t *__restrict__ xy, const uint8_t *__restrict__ flags, i
 
     // 1. compaction of flagged events in event order, in chunks of 256*16 events
     int n_cand = 0;
+    // 16-B flag loads where the slice's first ADDRESS is 16-B aligned (my0 is a multiple of 16)
+    const bool vec = ((reinterpret_cast<uintptr_t>(flags) + lo) & 15) == 0;  // uniform
     for (int64_t c0 = 0; c0 < len; c0 += kThreads * 16) {
         const int64_t my0 = c0 + (int64_t)tid * 16;
         uint32_t bits = 0;
-        if (my0 + 15 < len && ((lo + my0) & 15) == 0) {
+        if (my0 + 15 < len && vec) {
             const uint4 q = *reinterpret_cast<const uint4 *>(flags + lo + my0);
             const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
@@ -171,8 +173,9 @@ nms_compact_kernel(const uint32_t *__restrict__ xy, const uint8_t *__restrict__ 
     const int64_t len = ((lo + S < n) ? lo + S : n) - lo;
     int run = 0;
     // 16-B aligned slices: one unconditional 16-B load per lane through a buffer view of the
-    // slice rounded up to 16 B (the round-up stays inside the allocation's last 16-B block; bytes
-    // past len are masked) -- a per-lane choice of load form waited for every load
+    // slice rounded up to 16 B (the slice starts on a 16-B boundary in this arm, so the round-up ends
+    // with the 16-B block of its last byte; bytes past len are masked) -- a per-lane choice of load
+    // form waited for every load
     const bool vec = ((reinterpret_cast<uintptr_t>(flags) + lo) & 15) == 0;  // uniform
     const __amdgpu_buffer_rsrc_t vf = ecc::buffer_view(flags + lo, (uint32_t)((len + 15) & ~15ll));
     for (int64_t c0 = 0; c0 < len; c0 += kCompactThreads * 16) {

@@ -251,10 +251,11 @@ int radius_lists(ecc_ctx *ctx, const T *pts, int64_t n, int32_t dim, double eps,
     int rc = check_args(ctx, pts, n, dim, eps);
     if (rc) return rc;
     if (!counts || !offsets || nbr_cap < 0 || (nbr_cap > 0 && !nbr)) return ECC_ERR_INVALID;
-    if (n == 0) return ECC_OK;
     ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t s = ecc::as_stream(stream);
     ECC_CHECK_HIP(ctx, hipMemsetAsync(&ctx->dev->radius[0], 0, 4, s), "memset(radius err)");
+    // no points: the scan of no counts, offsets[0] = 0 (the entries needed), and a clean status
+    if (n == 0) return ecc::exclusive_scan_i32_i64(ctx, counts, 0, offsets, nullptr, s);
     if (!nbr) {  // size query: the offsets only (offsets[n] = entries needed)
         rc = ecc::ws_reserve(ctx, ecc::scan_scratch_bytes(n));
         if (rc) return rc;

@@ -18,6 +18,29 @@
  *
  * Reference interface each entry point replaces is cited on the declaration.
  * Quirk decisions (ref_compat vs fixed) follow SURVEY.md Appendix A.
+ *
+ * Alignment and extents.  Every device pointer needs only the natural alignment of its element
+ * type (4 B for uint32_t / int32_t / float and ecc_corner, 8 B for int64_t / double / uint64_t,
+ * none for uint8_t) unless its entry point says otherwise; the float k-means keeps its own notes
+ * (xy 8-byte aligned, 16-byte for engine 3).  Interior pointers (a shard's `xy + lo`, `flags + lo`)
+ * are therefore valid arguments.  Wider loads and stores are faster paths that a kernel selects by
+ * the ADDRESS it is about to touch (element index plus the pointer's own offset), never by the
+ * index alone; results do not depend on which path ran.  An entry point writes only the documented
+ * extent of its outputs and its results depend only on the documented extent of its inputs:
+ * whatever follows `n` events, a segment's count or a slice's count may hold anything.  Those
+ * bytes may be READ, though: a kernel may load up to 15 bytes past the documented end of an input
+ * (it masks what it loaded), so the caller keeps those bytes readable: true of any input that
+ * starts on a 16-byte boundary of a device allocation, and of an interior pointer whose input ends
+ * at least 16 bytes before its allocation does.
+ *
+ * Empty calls.  With n == 0 (n_segs, n_slices, n_points == 0) an entry point reads no input and
+ * writes no per-element output; it writes exactly the scalars that are defined for no input:
+ * k-means iters_out = 0; ecc_kmeans_counts_xy16 an all-zero count image; ecc_fast_detect_prepare an
+ * all-zero local_last; offsets[0] = 0 from ecc_corner_pack, ecc_eps_lists and ecc_radius_lists_*;
+ * *n_dups = 0 from ecc_dbscan_extract / _grid / _cloud_*, and n_clusters[0] = 0 from
+ * ecc_dbscan_cloud_*.  Two entries are defined for no input in full: ecc_sae_max_combine with
+ * n_images == 0 zeroes out[hw] (the initial SAE of the first shard), and ecc_kmeans_refcompat_f32
+ * with n == 0 runs the reference's loop over no points (see its entry).
  */
 #ifndef ECC_H
 #define ECC_H
@@ -201,7 +224,8 @@ int ecc_kmeans_run_f32_engine(ecc_ctx *ctx, const float *xy, int64_t n_points, c
  * running-maximum selective update, and the restart while that maximum is > 10 (Q9), at most
  * max_passes passes.  centroids16: DEVICE float[16] (x0, y0, .., x7, y7) in/out; passes_out
  * DEVICE int32[1], bin_counts_out DEVICE int32[8] (cluster_index) and partial_sums_out DEVICE
- * float[32] (the chunk sums) of the last pass, each may be NULL.  Bit-exact vs the oracle's
+ * float[32] (the chunk sums) of the last pass, each may be NULL.  n == 0 is the reference's loop
+ * over no points (a pass over empty bins) and writes every output.  Bit-exact vs the oracle's
  * orc_kmeans_refcompat, whose passes are pinned against the reference's kernels.  The product's
  * default is the "fixed" loop above (ecc_kmeans_run_*). */
 int ecc_kmeans_refcompat_f32(ecc_ctx *ctx, const float *xy, int64_t n, float *centroids16, int32_t max_passes,
@@ -336,8 +360,9 @@ int ecc_corner_nms_status(ecc_ctx *ctx, ecc_stream_t stream);
  * (FCT/…group_track.cpp:832-837: detect, then filterCorners on the slice's corners):
  * == ecc_fast_detect(ctx, xy, t, n, cfg, sae, corner_flags) then ecc_corner_nms(ctx, xy,
  * corner_flags, n, cfg->slice_events, cfg->width, cfg->height, box_size, cap, out, out_count),
- * same outputs and status calls.  With slices of at most 16384 events (a multiple of 4) the
- * flag pass writes the NMS candidate lists itself, so NMS does not re-read the flags. */
+ * same outputs and status calls.  With slices of at most 16384 events (a multiple of 4) and
+ * corner_flags 4-byte aligned the flag pass writes the NMS candidate lists itself, so NMS does not
+ * re-read the flags; otherwise the two calls run as they are. */
 int ecc_fast_detect_nms(ecc_ctx *ctx, const uint32_t *xy, const int64_t *t, int64_t n,
                         const ecc_corner_cfg *cfg, int64_t *sae, uint8_t *corner_flags, int32_t box_size,
                         int32_t cap, ecc_corner *out, int32_t *out_count, ecc_stream_t stream);
@@ -436,7 +461,9 @@ int ecc_tracker_set_tracks(ecc_tracker *tr, const ecc_track *tracks, int32_t n, 
  * Points are packed u16 xy, segmented like ecc_kmeans_run_xy16 (one independent
  * neighbourhood problem per segment, <= 16384 points each, e.g. one downsample window);
  * duplicates allowed.  Arrays are indexed by the flattened point index p = s*seg_stride + j
- * (entries with j >= seg_counts[s] are left untouched, except offsets which stay monotone).
+ * (entries with j >= seg_counts[s]: ecc_eps_counts writes counts[p] = 0 and core_dist[p] = -1, so
+ * that the scan over all of `counts` in ecc_eps_lists skips them and offsets stay monotone;
+ * ecc_eps_lists takes `counts` as ecc_eps_counts wrote it, padding entries included).
  *   counts[p]    = |{j in seg : (xi-xj)^2 + (yi-yj)^2 <= eps^2}| (self included);
  *   core_dist[p] = sqrt of the (min_pts-1)-th smallest d^2 of that set (fp64), or -1 when
  *                  counts[p] < min_pts (optics.hpp:292-298).  NULL to skip.
