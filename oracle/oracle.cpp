@@ -16,7 +16,9 @@
 //     (compiled from /root/reference by oracle/ref/Makefile, run on the GPU box through
 //     oracle/ref/ref_harness.c) — tests/test_ref_opencl.py;
 //   * OPTICS / kd-tree / epsilon estimation: pinned by the reference's assert KATs
-//     (OPT/test/test_main.cpp) transcribed into tests/golden/optics_kat.json;
+//     (OPT/test/test_main.cpp) transcribed into tests/golden/optics_kat.json; the ordering and
+//     the threshold clusters also by the reference's own compiled code (oracle/ref/ref_optics.cpp)
+//     — tests/test_ref_optics.py;
 //   * SAE/arc test, NMS, tracker, DBSCAN: the reference code is embedded in Metavision/OpenCV/PCL
 //     programs that cannot be built here without stand-in headers -> "parity unpinned" beyond
 //     hand-derived known-answer cases (tests/test_oracle_kat.py).
@@ -822,7 +824,7 @@ ORC_API int orc_radius_f32(const float *pts, int n, int dim, double eps, int min
 
 // a13: optics::compute_reachability_dists, OPT/include/optics/optics.hpp:413-565 with exact
 // eps-balls (the KDTREE back end's radius_search, kdTree.hpp:407-422, equals the exact ball
-// except for the tie case documented as quirk Q21).  Points are D-dim doubles (D <= 3).
+// except for the tie case documented as quirk Q22).  Points are D-dim doubles (D <= 3).
 // Output: order[i] = point index, reach[i] = reachability (-1 undefined).
 namespace {
 struct RD {

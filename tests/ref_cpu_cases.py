@@ -35,34 +35,38 @@ def sha(*parts):
     return h.hexdigest()
 
 
-def _ref(case, tmp_path, sub, inputs, args, outputs, digest_only=()):
+def _ref(case, tmp_path, sub, inputs, args, outputs, digest_only=(), exe=None, store=None, restore=None):
     """Runs `ref_cpu sub` (or loads the stored run).  inputs: {file name: array}; args: the argument
     list with input/output file NAMES in place of paths; outputs: {file name: dtype}.  Returns
     {output name: array}; an output in digest_only is returned whole from a live run and as
-    <name>_sha always."""
+    <name>_sha always.  exe: another binary of oracle/_ref/ (tests/ref_optics_cases.py).  store /
+    restore: the result dict -> the arrays a fixture keeps, and back (a smaller form of an output,
+    which restore must prove equal to what was recorded)."""
+    exe = REF_CPU if exe is None else exe
     key = sha(sub, [a for a in args if a not in inputs and a not in outputs],
               *[inputs[k] for k in sorted(inputs)])
     stored = GOLDEN / f"{case}.npz"
-    if REF_CPU.exists():
+    if exe.exists():
         d = tmp_path / f"ref_{case}"
         d.mkdir(exist_ok=True)
         for name, a in inputs.items():
             (d / name).write_bytes(np.ascontiguousarray(a).tobytes())
         argv = [str(d / a) if (a in inputs or a in outputs) else str(a) for a in args]
-        r = subprocess.run([str(REF_CPU), sub] + argv, capture_output=True, text=True, timeout=300)
+        r = subprocess.run([str(exe), sub] + argv, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr
         res = {name: np.frombuffer((d / name).read_bytes(), dt).copy() for name, dt in outputs.items()}
         for name in digest_only:
             res[name + "_sha"] = np.array(sha(res[name]))
         if os.environ.get("ECC_RECORD_REF_GOLDEN") == "1":
             GOLDEN.mkdir(parents=True, exist_ok=True)
-            np.savez_compressed(stored, input_sha=np.array(key),
-                                **{k: v for k, v in res.items() if k not in digest_only})
+            kept = {k: v for k, v in res.items() if k not in digest_only}
+            np.savez_compressed(stored, input_sha=np.array(key), **(store(kept) if store else kept))
         return res
-    assert stored.exists(), f"neither {REF_CPU} (reference tree absent at build time) nor {stored}"
+    assert stored.exists(), f"neither {exe} (reference tree absent at build time) nor {stored}"
     z = np.load(stored)
     assert str(z["input_sha"]) == key, f"{stored.name} answers another input: the generator changed, record it again"
-    return {k: z[k] for k in z.files if k != "input_sha"}
+    kept = {k: z[k] for k in z.files if k != "input_sha"}
+    return restore(kept) if restore else kept
 
 
 def same_surface(ref, got):
