@@ -14,26 +14,33 @@ int hip_fail(ecc_ctx *ctx, hipError_t e, const char *what) {
     return ECC_ERR_HIP;
 }
 
+int buf_reserve(ecc_ctx *ctx, DevBuffer &buf, size_t want_bytes, const char *what) {
+    if (want_bytes <= buf.bytes) return ECC_OK;
+    ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
+    if (buf.p) {
+        // Work already queued on any stream may still use the old buffer.
+        ECC_CHECK_HIP(ctx, hipDeviceSynchronize(), (std::string("hipDeviceSynchronize(") + what + " grow)").c_str());
+        (void)hipFree(buf.p);
+        buf = DevBuffer{};
+    }
+    const hipError_t e = hipMalloc(&buf.p, want_bytes);
+    if (e != hipSuccess) {
+        buf.p = nullptr;
+        hip_fail(ctx, e, (std::string("hipMalloc(") + what + ")").c_str());
+        return ECC_ERR_NOMEM;
+    }
+    buf.bytes = want_bytes;
+    return ECC_OK;
+}
+
 int ws_reserve(ecc_ctx *ctx, size_t bytes) {
     if (!ctx) return ECC_ERR_INVALID;
     if (bytes <= ctx->ws_bytes) return ECC_OK;
-    ECC_CHECK_HIP(ctx, hipSetDevice(ctx->device), "hipSetDevice");
-    if (ctx->ws) {
-        // Work already queued on any stream may still use the old buffer.
-        ECC_CHECK_HIP(ctx, hipDeviceSynchronize(), "hipDeviceSynchronize(ws grow)");
-        ECC_CHECK_HIP(ctx, hipFree(ctx->ws), "hipFree(ws)");
-        ctx->ws = nullptr;
-        ctx->ws_bytes = 0;
-    }
-    size_t want = align_up(bytes, 1 << 20);
-    hipError_t e = hipMalloc(&ctx->ws, want);
-    if (e != hipSuccess) {
-        ctx->ws = nullptr;
-        hip_fail(ctx, e, "hipMalloc(ws)");
-        return ECC_ERR_NOMEM;
-    }
-    ctx->ws_bytes = want;
-    return ECC_OK;
+    DevBuffer b{ctx->ws, ctx->ws_bytes};  // (the other files read ctx->ws and ctx->ws_bytes)
+    const int rc = buf_reserve(ctx, b, align_up(bytes, 1 << 20), "ws");
+    ctx->ws = b.p;
+    ctx->ws_bytes = b.bytes;
+    return rc;
 }
 
 int allow_dynamic_lds(ecc_ctx *ctx, const void *kernel, int bytes, const char *what) {
@@ -168,8 +175,8 @@ ECC_API int ecc_ctx_destroy(ecc_ctx *ctx) {
     hipDeviceSynchronize();
     for (auto &p : ctx->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : ctx->event_pool) hipEventDestroy(e);
-    ecc::corner_state_release(ctx);
-    ecc::nms_state_release(ctx);
+    if (ctx->corner_buf.p) hipFree(ctx->corner_buf.p);
+    if (ctx->nms_buf.p) hipFree(ctx->nms_buf.p);
     if (ctx->ws) hipFree(ctx->ws);
     if (ctx->dev) hipFree(ctx->dev);
     delete ctx;

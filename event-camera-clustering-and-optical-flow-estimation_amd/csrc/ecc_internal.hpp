@@ -27,7 +27,25 @@ struct EccTimingPair {
 
 namespace ecc {
 struct DevWords;
-}
+
+// A device allocation that only grows (ecc::buf_reserve below); freed by ecc_ctx_destroy.
+struct DevBuffer {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
+// What the corner entry points keep between calls (corners.hip).
+struct CornerState {
+    // diagnostics of the last detection (ecc_fast_detect_stats)
+    const uint32_t *n_over = nullptr;
+    int64_t n_items = 0, n_slices = 0, n_groups = 0;
+    // the unsorted-time verdict (ecc_fast_detect_status): every sort phase takes a fresh tag;
+    // status_src says what the last call left to report (0: nothing, an empty call -> OK;
+    // 1: a prepare-only call -> the pending word against prep_tag; 2: a finished call -> flags[0])
+    int32_t next_tag = 0, prep_tag = 0;
+    int status_src = 0;
+};
+}  // namespace ecc
 
 struct ecc_ctx {
     int device = 0;
@@ -41,6 +59,12 @@ struct ecc_ctx {
     // Scratch workspace, grown on demand (never inside a capture: call once eagerly first).
     void *ws = nullptr;
     size_t ws_bytes = 0;
+    // The corner stage's workspace: the sorted batch with its offset tables and the per-group images
+    // (sized by batch and sensor); it lives from a prepare to its finish, while other entry points use ws.
+    ecc::DevBuffer corner_buf;
+    ecc::CornerState corner;
+    // The NMS candidate lists (nms.hip): they live across a fused detect + NMS call.
+    ecc::DevBuffer nms_buf;
     // The kernels' status words and small device-side results (ecc::DevWords below).
     ecc::DevWords *dev = nullptr;
     // Largest dynamic-LDS grant made per kernel on this context's device (ecc::allow_dynamic_lds).
@@ -52,7 +76,7 @@ namespace ecc {
 // Device memory of the context that kernels write and the *_status calls read back: one member
 // per user, zeroed by ecc_ctx_create.  Each entry point clears its own member before it launches.
 struct DevWords {
-    int32_t fast_verdict;      // corners.hip: unsorted-time verdict of the last fast_detect
+    int32_t fast_verdict;      // corner_pairs.hip (sae_prefix): unsorted-time verdict of the last fast_detect
     int32_t nms;               // nms.hip (and the fused corner + NMS phases): bit 0 capacity, bit 1 outside
     int32_t eps_lists;         // eps.hip: the lists disagree with the counts, or nbr_cap exceeded
     int32_t evt;               // evt.hip: bit 1 capacity, bit 2 unsorted t
@@ -61,7 +85,7 @@ struct DevWords {
     int32_t radius[2];         // radius.hip: [0] bit 1 list capacity; radius_grid.hpp: [1] non-finite input
     int32_t dbscan_cloud;      // dbscan_cloud.hip: bit 1 duplicate capacity
     int32_t eps_left;          // eps.hip: segments the row-run counts left to the candidate walk
-    int32_t sort_pending;      // corners.hip: tag of the last sort phase that saw decreasing time
+    int32_t sort_pending;      // corner_sort.hip: tag of the last sort phase that saw decreasing time
     int32_t dbscan_left;       // dbscan.hip: segments dbscan_run_kernel left to dbscan_grid_kernel
     int32_t optics_xi[2];      // optics_xi.hip: [0] more pairs than cap, [1] the workspace check fired
     int32_t cluster_stats[2];  // cluster_stats.hip: [0] more runs than cap, [1] invalid order entry or pair
@@ -89,6 +113,11 @@ __device__ __forceinline__ int seg_points(const SegView &sv, int64_t s) { return
 
 // Records the HIP error on the context and returns ECC_ERR_HIP.
 int hip_fail(ecc_ctx *ctx, hipError_t e, const char *what);
+
+// Ensures `buf` holds >= want_bytes.  A buffer that is too small is freed (after a device
+// synchronise: queued work may still use it) and allocated anew, its contents lost; on failure it
+// is left empty, last_error names `what`, and the status is ECC_ERR_NOMEM.
+int buf_reserve(ecc_ctx *ctx, DevBuffer &buf, size_t want_bytes, const char *what);
 
 // Ensures the context workspace holds >= bytes (16-byte aligned carve base). Returns status.
 int ws_reserve(ecc_ctx *ctx, size_t bytes);
@@ -122,10 +151,6 @@ size_t scan_scratch_bytes(int64_t n);
 int exclusive_scan_i32_i64(ecc_ctx *ctx, const int32_t *in, int64_t n, int64_t *out, int64_t *scratch,
                            hipStream_t s);
 
-// Frees the per-context corner-stage workspace (corners.hip); called by ecc_ctx_destroy.
-void corner_state_release(const ecc_ctx *ctx);
-// Frees the per-context NMS candidate buffer (nms.hip); called by ecc_ctx_destroy.
-void nms_state_release(const ecc_ctx *ctx);
 // Grid NMS in two steps (nms.hip), so that a producer of the per-slice candidate lists (the
 // corner flag pass of ecc_fast_detect_nms) can replace nms_compact_kernel: the argument check of
 // ecc_corner_nms; the per-context candidate buffer (n xy words at cand[s * S ...], counts

@@ -23,9 +23,6 @@
 // kills the later lanes it overlaps).  ~2 KiB of LDS per slice, so many slices run per CU.
 #include "ecc_internal.hpp"
 
-#include <map>
-#include <mutex>
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -290,13 +287,6 @@ corner_pack_kernel(const ecc_corner *__restrict__ in, const int32_t *__restrict_
     for (int d = threadIdx.x; d < c; d += 256) out[o + d] = in[s * cap + d];
 }
 
-struct NmsState {
-    void *buf = nullptr;
-    size_t bytes = 0;
-};
-std::mutex g_nms_mu;
-std::map<const ecc_ctx *, NmsState> g_nms;
-
 }  // namespace
 
 namespace ecc {
@@ -317,27 +307,11 @@ int nms_candidates(ecc_ctx *ctx, int64_t n, int32_t slice_events, int32_t width,
     const int64_t n_slices = (n + slice_events - 1) / slice_events;
     // candidate lists: n xy words + n_slices counts, per context (grown, never shrunk)
     const size_t need = ecc::align_up((size_t)n * 4, 256) + (size_t)n_slices * 4;
-    NmsState *st;
-    {
-        std::lock_guard<std::mutex> lk(g_nms_mu);
-        st = &g_nms[ctx];
-    }
-    if (need > st->bytes) {
-        if (st->buf) {
-            ECC_CHECK_HIP(ctx, hipDeviceSynchronize(), "sync(nms buffer)");
-            (void)hipFree(st->buf);
-            st->buf = nullptr;
-            st->bytes = 0;
-        }
-        const size_t want = ecc::align_up(need + need / 8, 1 << 20);
-        if (hipMalloc(&st->buf, want) != hipSuccess) {
-            st->buf = nullptr;
-            return ECC_ERR_NOMEM;
-        }
-        st->bytes = want;
-    }
-    *cand = static_cast<uint32_t *>(st->buf);
-    *n_cand = reinterpret_cast<int32_t *>(static_cast<char *>(st->buf) + ecc::align_up((size_t)n * 4, 256));
+    if (need > ctx->nms_buf.bytes)
+        if (int rc = buf_reserve(ctx, ctx->nms_buf, ecc::align_up(need + need / 8, 1 << 20), "nms buffer")) return rc;
+    char *buf = static_cast<char *>(ctx->nms_buf.p);
+    *cand = reinterpret_cast<uint32_t *>(buf);
+    *n_cand = reinterpret_cast<int32_t *>(buf + ecc::align_up((size_t)n * 4, 256));
     return ECC_OK;
 }
 
@@ -415,13 +389,3 @@ ECC_API int ecc_corner_nms_status(ecc_ctx *ctx, ecc_stream_t stream) {
     if (f & 2) return ECC_ERR_INVALID;
     return (f & 1) ? ECC_ERR_CAPACITY : ECC_OK;
 }
-
-namespace ecc {
-void nms_state_release(const ecc_ctx *ctx) {
-    std::lock_guard<std::mutex> lk(g_nms_mu);
-    auto it = g_nms.find(ctx);
-    if (it == g_nms.end()) return;
-    if (it->second.buf) (void)hipFree(it->second.buf);
-    g_nms.erase(it);
-}
-}  // namespace ecc

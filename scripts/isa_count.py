@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static instruction counts per kernel of one HIP source, from the gfx950 assembly the Makefile's
+"""Static instruction counts per kernel of HIP sources, from the gfx950 assembly the Makefile's
 HIPFLAGS produce (hipcc -S --cuda-device-only).  CPU only: hipcc cross-compiles.
 
 Per kernel: instruction counts by class, s_barrier count, the metadata's .vgpr_count,
@@ -12,8 +12,8 @@ Classes go by mnemonic prefix only: v_ = VALU (v_readlane / v_writelane included
 global_ / buffer_ / flat_ / scratch_ = vector memory.  The counts are static: an instruction in a
 loop counts once, one on a rarely taken path counts like any other.
 
-Usage: isa_count.py [source.hip] [--kernels name,name] [--keep-asm out.s] [EXTRA_HIPFLAGS...]
-(default source: csrc/corners.hip)
+Usage: isa_count.py [source.hip ...] [--kernels name,name] [--keep-asm out.s] [EXTRA_HIPFLAGS...]
+(default sources: the corner stage files csrc/corner_{sort,pairs,arc,flags}.hip; --keep-asm takes one source)
 """
 import re
 import subprocess
@@ -128,11 +128,18 @@ def main():
         i = argv.index("--keep-asm")
         keep = argv[i + 1]
         del argv[i:i + 2]
-    srcs = [a for a in argv if a.endswith(".hip")]
+    srcs = [Path(a) for a in argv if a.endswith(".hip")]
     extra = [a for a in argv if not a.endswith(".hip")]
-    src = Path(srcs[0]) if srcs else PKG / "csrc" / "corners.hip"
+    srcs = srcs or [PKG / "csrc" / f"corner_{stage}.hip" for stage in ("sort", "pairs", "arc", "flags")]
+    if keep and len(srcs) != 1:
+        sys.exit("--keep-asm takes one source")
     hipcc = makefile_var("HIPCC")[0]
     flags = makefile_var("HIPFLAGS")
+    for src in srcs:
+        report(src, hipcc, flags, extra, only, keep)
+
+
+def report(src, hipcc, flags, extra, only, keep):
     with tempfile.TemporaryDirectory() as td:
         out = Path(keep) if keep else Path(td) / "out.s"
         subprocess.run([hipcc, *flags, *extra, "-fvisibility=hidden", "-S", "--cuda-device-only", str(src), "-o", str(out)],
@@ -140,13 +147,15 @@ def main():
         asm = out.read_text()
     funcs, meta = parse_functions(asm), parse_metadata(asm)
     syms = [s for s in funcs if s in meta]
+    rows = [(sym, name) for sym, name in zip(syms, demangle(syms))
+            if not only or name.split("<")[0].split()[-1] in only]  # a template's name: "void kernel<...>"
+    if not rows:
+        return
     print(f"# {src.name}: static gfx950 instruction counts (scripts/isa_count.py)")
     print(f"# flags: {' '.join(flags + extra)}")
     print(f"{'kernel':44s} {'valu':>5s} {'scal':>5s} {'lds':>4s} {'vmem':>4s} {'barr':>4s} {'vgpr':>4s} {'sspill':>6s} "
           f"{'vspill':>6s} {'lds_B':>6s}")
-    for sym, name in zip(syms, demangle(syms)):
-        if only and name.split("<")[0].split()[-1] not in only:  # a template's name: "void kernel<...>"
-            continue
+    for sym, name in rows:
         insts, loops = funcs[sym]
         c, m = count(insts), meta[sym]
         print(f"{name[:44]:44s} {c['valu']:5d} {c['scalar']:5d} {c['lds']:4d} {c['vmem']:4d} {c['barrier']:4d} "
@@ -158,7 +167,6 @@ def main():
             ahead = count(insts[:first])
             print(f"    loop {label:12s} {'':27s} {b['valu']:5d} {b['scalar']:5d} {b['lds']:4d} {b['vmem']:4d} {b['barrier']:4d}"
                   f"  (ahead of it: valu {ahead['valu']}, scal {ahead['scalar']})")
-
 
 if __name__ == "__main__":
     main()

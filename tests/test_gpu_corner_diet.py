@@ -1,5 +1,5 @@
 """Corner chain: the per-group records, the division-free item decode and the sort kernel's
-sentinel bins (csrc/corners.hip), at the smallest shapes where each can go wrong.  Every case
+sentinel bins (csrc/corner_common.hpp, corner_sort.hip), at the smallest shapes where each can go wrong.  Every case
 compares the flags and the final SAE with orc.fast_detect exactly.
 
 * Group records: slice_sort's workgroup of a group's first slice writes the group's constants

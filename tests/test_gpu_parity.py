@@ -1822,6 +1822,124 @@ def test_lds_grant_two_contexts_one_device(ecc):
     assert res["rc"] == [ecc.OK] * 4 and res["equal"] == [True, True], res
 
 
+# The corner batch, the NMS candidate buffer and the status bookkeeping are members of the context.
+def _corner_calls(ecc, ctx, cfg, d_xy, n):
+    """prepare(t) / finish(t) of the two-call form on `ctx` (raw status), with their outputs."""
+    hw = cfg.width * cfg.height
+    local, sae = ecc.DeviceArray(hw, np.int64), ecc.DeviceArray.zeros(hw, np.int64)
+    flags = ecc.DeviceArray(n, np.uint8)
+
+    def prepare(d_t):
+        return ecc.lib.ecc_fast_detect_prepare(ctx.ctx, d_xy.ptr, d_t.ptr, n, C.byref(cfg), local.ptr, ctx.stream)
+
+    def finish(d_t):
+        return ecc.lib.ecc_fast_detect_finish(ctx.ctx, d_xy.ptr, d_t.ptr, n, C.byref(cfg), sae.ptr, flags.ptr,
+                                              ctx.stream)
+
+    return prepare, finish, sae, flags
+
+
+def test_corner_state_two_contexts_interleaved(ecc, orc):
+    """Two contexts on device 0 with their two-call detections interleaved: each keeps its own
+    batch, verdict and statistics."""
+    W, H = W_SMALL, H_SMALL
+    cfg = ecc.corner_cfg(width=W, height=H, first_detect_slice=0)
+    na, nb = 40000, 20000  # 3 slices and 2
+    xy_a, t_a, _ = ecc.gen_events(na, seed=3)
+    xy_b, t_b, _ = ecc.gen_events(nb, seed=4)
+    bad = t_a.copy()
+    bad[30000] = bad[29999] - 7
+    a, b = ecc.Context(0), ecc.Context(0)
+    try:
+        d_xy_a, d_bad, d_ok_a = dev(ecc, xy_a), dev(ecc, bad), dev(ecc, t_a)
+        d_xy_b, d_t_b = dev(ecc, xy_b), dev(ecc, t_b)
+        prep_a, fin_a, sae_a, flags_a = _corner_calls(ecc, a, cfg, d_xy_a, na)
+        prep_b, fin_b, sae_b, flags_b = _corner_calls(ecc, b, cfg, d_xy_b, nb)
+        assert prep_a(d_bad) == ecc.OK and prep_b(d_t_b) == ecc.OK
+        assert a.fast_detect_status() == ecc.ERR_UNSORTED_TIME
+        assert b.fast_detect_status() == ecc.OK
+        assert fin_a(d_bad) == ecc.OK and fin_b(d_t_b) == ecc.OK
+        assert a.fast_detect_status() == ecc.ERR_UNSORTED_TIME
+        assert b.fast_detect_status() == ecc.OK
+        o_flags_b, o_sae_b = orc.fast_detect(xy_b, t_b, W, H, first_detect=0)
+        assert (flags_b.numpy() == o_flags_b).all() and (sae_b.numpy() == o_sae_b).all()
+        st_a, st_b = a.fast_detect_stats(), b.fast_detect_stats()
+        assert (st_a["slices"], st_a["groups"]) == (3, 1), st_a
+        assert (st_b["slices"], st_b["groups"]) == (2, 1), st_b
+        # a full sorted call on A: its own verdict and flags, B's statistics untouched
+        sae_a2 = ecc.DeviceArray.zeros(W * H, np.int64)
+        a.fast_detect(d_xy_a, d_ok_a, na, cfg, sae_a2, flags_a)
+        assert a.fast_detect_status() == ecc.OK
+        o_flags_a, o_sae_a = orc.fast_detect(xy_a, t_a, W, H, first_detect=0)
+        assert o_flags_a.sum() > 0 and o_flags_b.sum() > 0
+        assert (flags_a.numpy() == o_flags_a).all() and (sae_a2.numpy() == o_sae_a).all()
+        assert a.fast_detect_stats()["slices"] == 3 and b.fast_detect_stats() == st_b
+    finally:
+        a.close()
+        b.close()
+
+
+def test_corner_state_fresh_after_destroy(ecc):
+    """A context created after another was destroyed starts clean: no verdict, no statistics, and
+    no batch that a finish could run on."""
+    n = 40000
+    xy, t, _ = ecc.gen_events(n, seed=3)
+    bad = t.copy()
+    bad[30000] = bad[29999] - 7
+    cfg = ecc.corner_cfg(width=W_SMALL, height=H_SMALL, first_detect_slice=0)
+    d_xy, d_bad = dev(ecc, xy), dev(ecc, bad)
+    a = ecc.Context(0)
+    try:
+        prep, fin, _, _ = _corner_calls(ecc, a, cfg, d_xy, n)
+        assert prep(d_bad) == ecc.OK and fin(d_bad) == ecc.OK
+        assert a.fast_detect_status() == ecc.ERR_UNSORTED_TIME
+    finally:
+        a.close()
+    b = ecc.Context(0)
+    try:
+        assert b.fast_detect_status() == ecc.OK
+        assert b.fast_detect_stats() == {"items": 0, "overflow_items": 0, "slices": 0, "groups": 0}
+        _, fin, _, _ = _corner_calls(ecc, b, cfg, d_xy, n)
+        assert fin(d_bad) == ecc.ERR_INVALID  # finish without prepare
+    finally:
+        b.close()
+
+
+def test_corner_and_nms_buffers_regrow(ecc, orc):
+    """Fused detect + NMS at 16 384, 40 000 and 16 384 events on one context: the corner batch and
+    the NMS candidate buffer grow in the second call and are reused in the third.  Flags against
+    the oracle, kept corners against ecc_fast_detect + ecc_corner_nms on a second context."""
+    W, H, box, cap = W_SMALL, H_SMALL, 15, 64
+    cfg = ecc.corner_cfg(width=W, height=H, first_detect_slice=0)
+    xy, t, _ = ecc.gen_events(40000, seed=6)
+    d_xy, d_t = dev(ecc, xy), dev(ecc, t)
+    o_flags = {n: orc.fast_detect(xy[:n], t[:n], W, H, first_detect=0)[0] for n in (16384, 40000)}
+    assert all(f.sum() > 0 for f in o_flags.values())
+    a, b = ecc.Context(0), ecc.Context(0)
+    try:
+        for n in (16384, 40000, 16384):
+            ns = -(-n // cfg.slice_events)
+            got = []
+            for ctx, fused in ((a, True), (b, False)):
+                sae, flags = ecc.DeviceArray.zeros(W * H, np.int64), ecc.DeviceArray(n, np.uint8)
+                out, cnt = ecc.DeviceArray.zeros(ns * cap, ecc.CORNER_DTYPE), ecc.DeviceArray(ns, np.int32)
+                if fused:
+                    ctx.fast_detect_nms(d_xy, d_t, n, cfg, sae, flags, box, cap, out, cnt)
+                else:
+                    ctx.fast_detect(d_xy, d_t, n, cfg, sae, flags)
+                    ctx.corner_nms(d_xy, flags, n, cfg.slice_events, W, H, box, cap, out, cnt)
+                assert ctx.fast_detect_status() == ecc.OK
+                got.append((flags.numpy(), cnt.numpy(), out.numpy(), ctx.corner_nms_status()))
+            (f_a, c_a, o_a, s_a), (f_b, c_b, o_b, s_b) = got
+            assert (f_a == o_flags[n]).all() and (f_b == o_flags[n]).all(), n
+            assert s_a == s_b and (c_a == c_b).all(), n
+            for s in range(ns):
+                assert (o_a[s * cap: s * cap + c_a[s]] == o_b[s * cap: s * cap + c_b[s]]).all(), (n, s)
+    finally:
+        a.close()
+        b.close()
+
+
 # ------------------------------------------------------------------------------ HIP graph replay
 def test_graph_replay_matches_eager(ecc, orc, gpu):
     """ecc_graph_begin/end/launch: a captured downsample -> k-means -> corners -> NMS step replays

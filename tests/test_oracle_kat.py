@@ -107,7 +107,7 @@ def test_kmeans_refcompat_runs(orc):
 
 
 def _count_formulation(v, smin, smax):
-    """The GPU's branch-free form of the arc test (csrc/corners.hip arc_streak)."""
+    """The GPU's branch-free form of the arc test (csrc/arc_select.hpp arc_streak)."""
     n = len(v)
     cnt = np.array([(v > v[j]).sum() for j in range(n)])
     for s in range(smin, smax + 1):
