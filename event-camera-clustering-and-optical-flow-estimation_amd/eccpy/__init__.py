@@ -151,6 +151,8 @@ _sigs = {
     "ecc_kmeans_accumulate_xy16": (C.c_int, [P, P, i64, i64, P, P, i32, C.c_float, P, P, P]),
     "ecc_kmeans_update": (C.c_int, [P, P, P, i32, C.c_float, P, P]),
     "ecc_kmeans_labels_xy16": (C.c_int, [P, P, i64, i64, P, P, i32, C.c_float, P, P]),
+    "ecc_kmeans_windows_xy16": (C.c_int, [P, P, i64, i64, P, C.POINTER(KmeansCfg), P, P, P, P, P, P]),
+    "ecc_kmeans_windows_flow_host": (C.c_int, [P, P, i64, i32, P, P]),
     "ecc_kmeans_counts_xy16": (C.c_int, [P, P, i64, i64, P, i32, i32, P, P]),
     "ecc_kmeans_counts_status": (C.c_int, [P, P]),
     "ecc_kmeans_run_counts": (C.c_int, [P, P, i32, i32, C.POINTER(KmeansCfg), P, P, P]),
@@ -230,6 +232,7 @@ _sigs = {
     "ecc_dist_corner_slices": (C.c_int, [P, P, P, i32, i64, i64, P, P, P]),
 }
 DIST_ID_BYTES = 128
+KMEANS_WINDOWS_MAX_GRID = 2048  # ECC_KMEANS_WINDOWS_MAX_GRID: workgroups of one ecc_kmeans_windows_xy16 launch
 for _name, (_res, _args) in _sigs.items():
     _f = getattr(lib, _name)  # every bound symbol must exist (fail loudly on a stale build)
     _f.restype = _res
@@ -394,6 +397,16 @@ class Context:
         check(lib.ecc_kmeans_run_xy16_frame(self.ctx, xy.ptr, n_segs, stride, _ptr(counts), w, h, C.byref(cfg),
                                             centroids.ptr, _ptr(labels), _ptr(iters), self.stream),
               "ecc_kmeans_run_xy16_frame")
+
+    def kmeans_windows(self, xy: DeviceArray, n_segs: int, stride: int, counts: DeviceArray | None, cfg: KmeansCfg,
+                       init: DeviceArray | None, centroids: DeviceArray, labels: DeviceArray | None = None,
+                       sizes: DeviceArray | None = None, iters: DeviceArray | None = None):
+        """k-means per window, all windows in one launch: centroids float32[n_segs * 2k] (row s = window s;
+        in/out when init is None, else every window starts from init float32[2k]); labels uint8[n_segs * stride]
+        (written inside the counts only), sizes int32[n_segs * k] and iters int32[n_segs] are optional."""
+        check(lib.ecc_kmeans_windows_xy16(self.ctx, _ptr(xy), n_segs, stride, _ptr(counts), C.byref(cfg), _ptr(init),
+                                          _ptr(centroids), _ptr(labels), _ptr(sizes), _ptr(iters), self.stream),
+              "ecc_kmeans_windows_xy16")
 
     def kmeans_f32(self, xy: DeviceArray, n: int, centroids: DeviceArray, cfg: KmeansCfg,
                    labels: DeviceArray | None = None, iters: DeviceArray | None = None):
@@ -718,6 +731,20 @@ def kmeans_cfg(**kw) -> KmeansCfg:
     for k, v in kw.items():
         setattr(c, k, v)
     return c
+
+
+def kmeans_windows_flow(centroids, sizes, k: int):
+    """Per-centre displacement of every window against the previous one (ecc_kmeans_windows_flow_host) from the
+    host copies of kmeans_windows' centroids and sizes: (diff float32[n, k, 2], has_prev uint8[n, k])."""
+    c = np.ascontiguousarray(centroids, np.float32).reshape(-1)
+    sz = np.ascontiguousarray(sizes, np.int32).reshape(-1)
+    if k < 1 or sz.size % k or c.size != 2 * sz.size:
+        raise EccError(ERR_INVALID, "kmeans_windows_flow: array sizes")
+    n = sz.size // k
+    diff, has_prev = np.zeros(max(c.size, 1), np.float32), np.zeros(max(sz.size, 1), np.uint8)
+    check(lib.ecc_kmeans_windows_flow_host(c.ctypes.data, sz.ctypes.data, n, k, diff.ctypes.data,
+                                           has_prev.ctypes.data), "ecc_kmeans_windows_flow_host")
+    return diff[:c.size].reshape(n, k, 2), has_prev[:sz.size].reshape(n, k)
 
 
 def corner_cfg(**kw) -> CornerCfg:

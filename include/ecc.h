@@ -246,6 +246,36 @@ int ecc_kmeans_update(ecc_ctx *ctx, uint64_t *acc, float *centroids, int32_t k, 
 int ecc_kmeans_labels_xy16(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int64_t seg_stride,
                            const int32_t *seg_counts, const float *centroids, int32_t k,
                            float threshold, uint8_t *labels, ecc_stream_t stream);
+/* k-means per downsample window, all windows in one launch (the reference's downsample -> cluster
+ * chain fits its centres per slice: DSA/…opencl_store.cpp:389-445, 470-518, TWE/…:396-448).  Every
+ * segment is its own "fixed"-mode Lloyd problem under the rules above; segment s's result is what
+ * ecc_kmeans_run_xy16 returns for that segment alone (n_segs = 1, same cfg and starting centres).
+ * xy / seg_stride / seg_counts: the downsample layout, 1 <= seg_stride <= 16384; seg_counts NULL =
+ * every segment full (NOT the dense form of the entries above), a count is clamped to
+ * [0, seg_stride].  init: DEVICE float[2k], the starting centres of every segment (centroids is
+ * then output only), or NULL: segment s starts from its own row of centroids (in/out).
+ * centroids: DEVICE float[n_segs*2k], row s = segment s's centres.  Optional outputs (NULL to
+ * skip): labels DEVICE uint8[n_segs*seg_stride], written at s*seg_stride + j for j < count_s only;
+ * sizes DEVICE int32[n_segs*k], sizes[s*k + c] = the points of segment s whose final label is c;
+ * iters DEVICE int32[n_segs], the updates done per segment.  An empty segment runs the loop over
+ * no points: centres unchanged, sizes 0, iters 1 when tol >= 0 and max_iters >= 1, else max_iters.
+ * All arguments are checked on the host, also when n_segs == 0 (then only the data pointers may be
+ * NULL, and nothing is written).  Nothing has a capacity, so there is no status call; the call
+ * allocates nothing and never synchronises (it can be captured by ecc_graph_*).  One workgroup per
+ * segment, at most ECC_KMEANS_WINDOWS_MAX_GRID of them (further segments are strided over). */
+#define ECC_KMEANS_WINDOWS_MAX_GRID 2048
+int ecc_kmeans_windows_xy16(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int64_t seg_stride,
+                            const int32_t *seg_counts, const ecc_kmeans_cfg *cfg, const float *init,
+                            float *centroids, uint8_t *labels, int32_t *sizes, int32_t *iters,
+                            ecc_stream_t stream);
+/* HOST: the reference's per-id displacement of a slice's centroids against the previous slice
+ * (TWE/…opencl_store.cpp:396-448, unscaled) on the host copies of ecc_kmeans_windows_xy16's
+ * centroids [n_segs*2k] and sizes [n_segs*k].  For window w >= 1 and centre c:
+ * has_prev[w*k + c] = sizes[w-1][c] > 0 && sizes[w][c] > 0, and diff[w*2k + 2c .. +1] = c_w - c_{w-1}
+ * (float subtraction) where has_prev, else 0.  Window 0: has_prev = 0, diff = 0.  n_segs == 0
+ * writes nothing.  ECC_ERR_INVALID: k < 1, n_segs < 0 or a NULL array. */
+int ecc_kmeans_windows_flow_host(const float *centroids, const int32_t *sizes, int64_t n_segs, int32_t k,
+                                 float *diff, uint8_t *has_prev);
 /* Count-image form (multi-GPU: ONE all-reduce per k-means instead of one per Lloyd pass).
  * ecc_kmeans_counts_xy16 writes counts[y*frame_w + x] (u32) = the number of points at (x, y)
  * (a point outside the frame sets the flag ecc_kmeans_counts_status reports as

@@ -25,6 +25,9 @@
 //                                    PCC/DBSCAN_simple.h:14-143, DBSCAN_precomp.h  ecc::DBSCANSimpleCluster ...
 //   process_coordinates + host slice path  SMP/…opencl_store.cpp:250-417  ecc::HashDownsampler
 //   assign_to_centers + k-means host loop  KM/assign_to_centers2.c:184-548 ecc::KMeans
+//   the same loop per slice + centroid - centroid_prev[id]
+//                                    DSA/…opencl_store.cpp:389-445, TWE/…:396-448  ecc::KMeans::fit_windows,
+//                                                                  ecc::window_centroid_flow
 //   aggregate lambda (batch SAE + arc test) FCT/…group_track.cpp:884-1070  ecc::TimeSurfaceCornerDetector
 //
 // Errors: the C ABI returns negative ecc_status codes; this layer throws ecc::Error (the
@@ -268,11 +271,32 @@ class KMeans {  // assign_to_centers + host loop, "fixed" mode (Appendix A Q7-Q1
     static int fit_ref_compat(Context &ctx, const std::vector<std::array<float, 2>> &points,
                               std::array<float, 16> &centroids, int max_passes = 50,
                               std::array<int32_t, 8> *bin_counts = nullptr);
+    // k-means per downsample window, all windows in one launch (ecc_kmeans_windows_xy16): xy holds
+    // window w's packed points at w * stride + j, j < counts[w] (counts empty: every window full),
+    // and xy.size() is a multiple of stride.  Every window starts from `init` (k centres).
+    struct Windows {
+        int64_t n_windows = 0;
+        std::vector<float> centroids;  // [n_windows * 2k]
+        std::vector<uint8_t> labels;   // [n_windows * stride], set for j < counts[w] (else 255)
+        std::vector<int32_t> sizes;    // [n_windows * k]
+        std::vector<int32_t> iters;    // [n_windows]
+    };
+    Windows fit_windows(const std::vector<uint32_t> &xy, int64_t stride, const std::vector<int32_t> &counts,
+                        const std::vector<std::array<float, 2>> &init);
 
   private:
     Context &ctx_;
     ecc_kmeans_cfg cfg_;
 };
+
+// Per-id displacement of every window's centroids against the previous window's (the reference
+// draws it per slice, TWE/…opencl_store.cpp:396-448; ecc_kmeans_windows_flow_host): diff
+// [n_windows * 2k] and has_prev [n_windows * k] from KMeans::Windows' centroids and sizes.
+struct WindowFlow {
+    std::vector<float> diff;
+    std::vector<uint8_t> has_prev;
+};
+WindowFlow window_centroid_flow(const std::vector<float> &centroids, const std::vector<int32_t> &sizes, int k);
 
 // ------------------------------------------------------------------------------ AEClustering
 // Host restatement of the reference's downsample consumer:
