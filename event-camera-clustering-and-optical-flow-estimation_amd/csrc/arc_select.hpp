@@ -1,6 +1,7 @@
-// The arc test's sorting and selection helpers, shared by arc_kernel and arc_dense_kernel.
-// Plain C++: compiles for the host too (tests/arc_select_probe.cpp runs every 0/1 input through
-// the networks there and checks arc_keys against arc_streak's count form).
+// The arc test's sorting and selection helpers and its maps to clamped keys, shared by arc_kernel
+// and arc_dense_kernel.  Plain C++: compiles for the host too (tests/arc_select_probe.cpp runs
+// every 0/1 input through the networks there, checks arc_keys against arc_streak's count form and
+// the clamps over the int64 edges).
 #pragma once
 #include <cstdint>
 
@@ -158,4 +159,38 @@ ECC_SEL_HD int arc_keys(uint32_t (&keys)[N], bool ties_exact) {
         }
     }
     return ok ? 1 : 0;
+}
+
+// ---- the maps from surface values to clamped keys ---------------------------------------------
+// v' = clamp(v - L, 0, vmax) for a narrow group: L + vmax is the group's last timestamp (below
+// 2^53 in magnitude, so L + vmax cannot overflow), L may be negative.  A value above the range
+// cannot be keyed: it raises *exact_flag (the item takes the exact int64 tests) and maps to vmax.
+// The range is checked BEFORE the subtraction: v - L leaves int64 for v near INT64_MAX under a
+// negative L (the difference used to wrap, and a wrapped key raised no flag).
+//
+// arc_kernel's: `inside` says the lane's pixel is on the sensor.  A lane outside it carries
+// INT64_MAX, which no test reads and which must not send the item away; a pixel of the surface
+// that really holds INT64_MAX is the newest value of its circles and does.
+ECC_SEL_HD uint32_t arc_clamp_value(int64_t v, int64_t L, uint32_t vmax, bool narrow, bool inside, int32_t *exact_flag) {
+    if (!narrow || v <= L) return 0u;
+    if (v > L + (int64_t)vmax) {
+        if (inside) *exact_flag = 1;
+        return vmax;
+    }
+    return (uint32_t)(v - L);
+}
+
+// arc_dense_kernel's (narrow groups, pixels on the sensor): a value at or below L that is not the
+// window minimum vz also raises *mixed_flag (ties among the keys at 0 may then be artefacts).
+ECC_SEL_HD uint32_t arc_clamp_rel(int64_t v, int64_t L, int64_t vz, uint32_t vmax, int32_t *exact_flag,
+                                  int32_t *mixed_flag) {
+    if (v <= L) {
+        if (v != vz) *mixed_flag = 1;
+        return 0u;
+    }
+    if (v > L + (int64_t)vmax) {
+        *exact_flag = 1;
+        return vmax;
+    }
+    return (uint32_t)(v - L);
 }

@@ -61,22 +61,10 @@ struct ArcLds {
     int32_t wave_tasks[16];  // the wave's eligible pairs (task-list offsets by a scan)
 };
 
-// arc_dense_kernel's clamp: v <= L maps to 0 (mixed_flag set when v is not the window minimum vz)
-__device__ __forceinline__ uint32_t clamp_rel(int64_t v, int64_t L, int64_t vz, int32_t *exact_flag,
-                                              int32_t *mixed_flag) {
-    if (v <= L) {
-        if (v != vz) *mixed_flag = 1;
-        return 0u;
-    }
-    const int64_t d = v - L;
-    if (d > (int64_t)kVMax) { *exact_flag = 1; return kVMax; }
-    return (uint32_t)d;
-}
-
 // The clamped B_g values (at or below L) are "mixed" when not all equal: ties among their keys may
 // then be artefacts of the clamp.  Per wave: its first clamped value c0 and flags cf (bit 1: it has
 // one, bit 0: another differs), by ballots and readlanes (no 64-bit reductions); bq = INT64_MAX
-// outside the sensor.
+// outside the sensor (never at or below Lt).
 __device__ __forceinline__ int64_t readlane_i64(int64_t v, int l) {
     return (int64_t)((uint64_t)__builtin_amdgcn_readlane((uint32_t)((uint64_t)v >> 32), l) << 32 |
                      (uint64_t)__builtin_amdgcn_readlane((uint32_t)v, l));
@@ -104,16 +92,8 @@ __device__ __forceinline__ bool clamp_mixed(const int64_t *wc0, const int32_t *w
     }
     return mixed;
 }
-// clamp(B_g - L, 0, 2^27 - 1); above the range the window goes to the exact test (*exact_flag)
-__device__ __forceinline__ uint32_t clamp_value(int64_t bq, int64_t Lt, bool narrow, int32_t *exact_flag) {
-    if (!narrow || bq == INT64_MAX || bq <= Lt) return 0u;
-    const int64_t d = bq - Lt;
-    if (d > (int64_t)kVMax) {
-        *exact_flag = 1;
-        return kVMax;
-    }
-    return (uint32_t)d;
-}
+// (arc_clamp_value and arc_clamp_rel, the maps to clamped keys, are in arc_select.hpp: the host runs them
+// over the int64 edges)
 
 // slices 0 .. j (j <= 31: 2u << 31 is 0 in 32 bits, so j = 31 gives all ones without a select)
 __device__ __forceinline__ uint32_t below_mask(int j) { return (2u << j) - 1u; }
@@ -276,7 +256,7 @@ __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const in
     const int wx = x0 + ox, wy = y0 + oy;
     const bool in = win_lane && wx >= 0 && wy >= 0 && wx < g.W && wy < g.H;
     const int64_t q = grp * HW + (int64_t)wy * g.W + wx;
-    int64_t bq = INT64_MAX;  // INT64_MAX: outside (never read)
+    int64_t bq = INT64_MAX;  // outside: never read (the window minimum skips it; `in` tells it from a real INT64_MAX)
     uint32_t mk = 0u;
     uint4 rec = make_uint4(0u, 0u, 0u, 0u);
     if (in) {
@@ -341,7 +321,7 @@ __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const in
         int64_t vz = INT64_MAX;
 #pragma unroll
         for (int w = 0; w < NT / 64; ++w) vz = L.wave_min[w] < vz ? L.wave_min[w] : vz;
-        L.mb[wp].bc = (!narrow || bq == INT64_MAX) ? 0u : clamp_rel(bq, Lt, vz, &L.exact_only, &L.mixed);
+        L.mb[wp].bc = (!narrow || !in) ? 0u : arc_clamp_rel(bq, Lt, vz, kVMax, &L.exact_only, &L.mixed);
     }
     __syncthreads();
     DENSE_MARK(2);  // (c)
@@ -544,6 +524,8 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
     const uint32_t mk_w = pre.mk;
     const int ox = wp % kWin - kHalo, oy = wp / kWin - kHalo;  // pixel relative to the tile origin
     const bool own = win_lane && ox >= 0 && oy >= 0 && ox < kTile && oy < kTile;
+    // on the sensor (a lane mask, taken here where ox and oy are live; arc_clamp_value reads it after barrier 1)
+    const bool inside = (unsigned)(x0 + ox) < (unsigned)g.W && (unsigned)(y0 + oy) < (unsigned)g.H;
     for (int w = tid; w < kPairWords; w += kArcThreads) L.res[w] = 0u;
     if (tid == 0) {
         L.exact_only = narrow ? 0 : 1;  // wide groups: every test exact
@@ -614,7 +596,7 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
         return;
     }
     if (win_lane) {
-        const uint32_t bcv = clamp_value(bq, Lt, narrow, &L.exact_only);  // above the range: the exact kernel
+        const uint32_t bcv = arc_clamp_value(bq, Lt, kVMax, narrow, inside, &L.exact_only);  // above the range: the exact kernel
         reinterpret_cast<uint2 *>(L.pix)[wp] = make_uint2(mk_w, (uint32_t)off);
         uint32_t *dst = L.vals + off;
         dst[0] = bcv;

@@ -248,10 +248,13 @@ __device__ __forceinline__ GroupRef group_ref(const int64_t *__restrict__ t, con
     r.first = grp * kGroup * (int64_t)g.S;
     const int64_t end = (grp + 1) * kGroup * (int64_t)g.S;
     r.t_first = t[r.first];
-    r.Lt = t[(end < g.n ? end : g.n) - 1] - (int64_t)kVMax;
+    const int64_t t_last = t[(end < g.n ? end : g.n) - 1];
+    // (in uint64: a group that ends within 2^27 of INT64_MIN is beyond double and never reads Lt, but
+    // the subtraction must not overflow a signed type)
+    r.Lt = (int64_t)((uint64_t)t_last - (uint64_t)kVMax);
     // any order: the span of the first and last timestamps says nothing about the others
-    r.narrow = !g.any_order && !beyond_double(r.t_first, r.Lt + (int64_t)kVMax) &&
-               (r.Lt + (int64_t)kVMax) - r.t_first < (int64_t)kVMax;
+    // (the span is taken only below 2^53 in magnitude: no overflow)
+    r.narrow = !g.any_order && !beyond_double(r.t_first, t_last) && t_last - r.t_first < (int64_t)kVMax;
     r.dlt = r.narrow ? (uint32_t)(r.t_first - r.Lt) : 0u;
     return r;
 }
@@ -266,7 +269,7 @@ __device__ __forceinline__ GroupRec group_rec_make(const int64_t *__restrict__ t
     rec.dlt = r.dlt;
     rec.bits = (r.narrow ? kRecNarrow : 0u) | (group_fmt4(t, g, grp) ? kRecFmt4 : 0u) |
                (group_narrow(t, g, grp, &t_first) ? kRecNarrow32 : 0u) |
-               (beyond_double(r.t_first, r.Lt + (int64_t)kVMax) ? kRecBeyond : 0u);
+               (beyond_double(r.t_first, (int64_t)((uint64_t)r.Lt + (uint64_t)kVMax)) ? kRecBeyond : 0u);
     return rec;
 }
 

@@ -311,7 +311,9 @@ int ecc_kmeans_assign_f32(ecc_ctx *ctx, const float *xy, int64_t n_points, const
  * Slices with global index < first_detect_slice are not tested (Q15: pass 1 for a fresh
  * stream, 0 when continuing a stream).
  * sae: DEVICE int64[H*W], row-major, holds the initial SAE on entry and the final SAE on
- * exit (stream continuation / multi-GPU hand-off).  Timestamps must be non-decreasing
+ * exit (stream continuation / multi-GPU hand-off).  Its values are any int64 as well, INT64_MIN
+ * and INT64_MAX included, above the batch's timestamps or below them (a window that holds a value
+ * above its group's last timestamp takes the exact test).  Timestamps must be non-decreasing
  * (Metavision stream order) -> ECC_ERR_UNSORTED_TIME otherwise (flag checked on device,
  * reported by ecc_fast_detect_status()).
  * corner_flags: DEVICE uint8[n], 1 = corner.  Bit-exact vs oracle/.

@@ -5,7 +5,10 @@
 //   * 10^5 random key sets with heavy ties per circle against std::sort;
 //   * arc_keys against the count form (arc_streak) on the same kind of values, with clamped zeros:
 //     the verdict where the keys decide, and the undecidable return exactly where fewer than
-//     SMAX + 1 values are unclamped and ties are not exact.
+//     SMAX + 1 values are unclamped and ties are not exact;
+//   * arc_clamp_value and arc_clamp_rel over the int64 edges against 128-bit arithmetic: L negative,
+//     zero and positive up to the ends of the narrow groups' range (+-2^53), v from INT64_MIN to
+//     INT64_MAX with L, L + 1, L + vmax and L + vmax + 1 in between, on and off the sensor.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -86,6 +89,47 @@ static bool keys_vs_count(int rounds, uint64_t *undecided) {
     return true;
 }
 
+// clamp(v - L, 0, vmax) and its flags in arithmetic that cannot overflow
+static bool clamp_edges() {
+    constexpr uint32_t vmax = (1u << 27) - 1u;
+    const int64_t two53 = (int64_t)1 << 53;
+    // L = t_last - vmax for t_last from the bottom to the top of the narrow groups' range
+    const int64_t Ls[] = {-two53 + 1 - (int64_t)vmax, -two53, -((int64_t)1 << 40), -(int64_t)vmax - 1, -(int64_t)vmax,
+                          -(int64_t)vmax + 1, -5, -1, 0, 1, 1000, (int64_t)1 << 30, two53 - 1 - (int64_t)vmax};
+    bool ok = true;
+    for (const int64_t L : Ls) {
+        const int64_t vs[] = {INT64_MIN, INT64_MIN + 1, L - 1, L, L + 1, L + 2, L + (int64_t)vmax - 1, L + (int64_t)vmax,
+                              L + (int64_t)vmax + 1, L + (int64_t)vmax + 2, 0, -1, 1, (int64_t)1 << 62, -((int64_t)1 << 62),
+                              INT64_MAX - (int64_t)vmax, INT64_MAX - 1, INT64_MAX};
+        for (const int64_t v : vs) {
+            const __int128 d = (__int128)v - (__int128)L;
+            const uint32_t want = d <= 0 ? 0u : d > (__int128)vmax ? vmax : (uint32_t)d;
+            const bool above = d > (__int128)vmax, low = d <= 0;
+            for (int narrow = 0; narrow < 2; ++narrow)
+                for (int inside = 0; inside < 2; ++inside) {
+                    int32_t ex = 0;
+                    const uint32_t got = arc_clamp_value(v, L, vmax, narrow != 0, inside != 0, &ex);
+                    const bool good = narrow ? got == want && ex == (above && inside ? 1 : 0) : got == 0u && ex == 0;
+                    if (!good) {
+                        std::printf("arc_clamp_value(v=%lld, L=%lld, narrow=%d, inside=%d) = %u, flag %d\n", (long long)v,
+                                    (long long)L, narrow, inside, got, ex);
+                        ok = false;
+                    }
+                }
+            for (const int64_t vz : {v, INT64_MIN, L}) {
+                int32_t ex = 0, mixed = 0;
+                const uint32_t got = arc_clamp_rel(v, L, vz, vmax, &ex, &mixed);
+                if (got != want || ex != (above ? 1 : 0) || mixed != (low && v != vz ? 1 : 0)) {
+                    std::printf("arc_clamp_rel(v=%lld, L=%lld, vz=%lld) = %u, flags %d %d\n", (long long)v, (long long)L,
+                                (long long)vz, got, ex, mixed);
+                    ok = false;
+                }
+            }
+        }
+    }
+    return ok;
+}
+
 int main() {
     uint64_t und = 0;
     bool ok = zero_one<16, 7, false>() && zero_one<20, 9, false>() &&
@@ -94,6 +138,7 @@ int main() {
          random_ties<20, 9, false>(100000) && random_ties<20, 9, true>(100000);
     ok = ok && keys_vs_count<16, 3, 6, false>(100000, &und) &&
          keys_vs_count<20, 4, 8, false>(100000, &und) && keys_vs_count<20, 4, 8, true>(100000, &und);
+    ok = ok && clamp_edges();
     std::printf("%s undecided=%llu\n", ok ? "OK" : "FAILED", (unsigned long long)und);
     return ok && und > 0 ? 0 : 1;
 }

@@ -20,6 +20,8 @@ from pathlib import Path
 
 import numpy as np
 
+import arc_path_cases as ap
+
 ROOT = Path(__file__).resolve().parent.parent
 REF_CPU = ROOT / "oracle" / "_ref" / "ref_cpu"
 GOLDEN = Path(__file__).resolve().parent / "golden" / "ref_cpu"
@@ -277,7 +279,20 @@ def stream_2p53(ecc, n, seed, cross_at, slice_events=SLICE, bursts_per_slice=150
     return xy, (1 << 53) - rel[cross_at] + rel
 
 
-ARC_CASES = ("gen", "border_mid", "interior", "sae0", "ties", "groups40")
+ARC_CASES = ("gen", "border_mid", "interior", "sae0", "ties", "groups40", "raster", "future_sae", "neg_time")
+PATCH, PATCH_B = (600, 300), (700, 400)  # where the 56 x 42 streams of tests/arc_path_cases.py sit in the frame
+PARK = (100, 100)                        # their off-sensor events: one interior pixel far from the patches
+
+
+def at_patch(xy, origin):
+    """An arc_path_cases stream's pixels moved to `origin`; its events off the 56 x 42 sensor to PARK."""
+    x, y = ap.unpack(xy)
+    on = (x < ap.W) & (y < ap.H)
+    return ap.pack(np.where(on, x + origin[0], PARK[0]), np.where(on, y + origin[1], PARK[1]))
+
+
+def patch_surface(sae, small, origin):
+    sae.reshape(H, W)[origin[1]: origin[1] + ap.H, origin[0]: origin[0] + ap.W] = small.reshape(ap.H, ap.W)
 _arc_cache = {}
 
 
@@ -303,6 +318,21 @@ def arc_case(ecc, name):
     elif name == "groups40":     # 40 slices: two of the device's 32-slice groups
         sl = 4096
         xy, t = stream_interior(ecc, 40 * sl, 5)
+    elif name == "raster":       # arc_path_cases.queue_full: more corners in a tile and group than the arc kernels queue
+        c = ap.queue_full()
+        xy, t, sl, first = at_patch(c["xy"], PATCH), c["t"], c["S"], 0
+    elif name == "future_sae":   # arc_path_cases.future_sae c (up to INT64_MAX) at PATCH and d (down to INT64_MIN) at PATCH_B
+        c, d = ap.future_sae("c", extra=2), ap.future_sae("d", extra=2)
+        sl, first = 2 * c["S"], 0
+        xy = np.stack([at_patch(c["xy"], PATCH).reshape(-1, c["S"]), at_patch(d["xy"], PATCH_B).reshape(-1, d["S"])],
+                      1).reshape(-1)  # every slice: c's events, then d's (they share no pixel)
+        t = ap.rising(len(xy), seed=21)
+        sae0 = np.zeros(W * H, np.int64)
+        patch_surface(sae0, c["sae0"], PATCH)
+        patch_surface(sae0, d["sae0"], PATCH_B)
+    elif name == "neg_time":     # arc_path_cases.negative_time: crosses zero inside a slice, over a zero surface
+        c = ap.negative_time("cross_zero", extra=3)
+        xy, t, sl, first = at_patch(c["xy"], PATCH), c["t"], c["S"], 0
     elif name == "t53":          # passes 2^53 in the middle of slice 2
         xy, t = stream_2p53(ecc, n, 6, 2 * SLICE + 8000)
     elif name == "t53_groups40":  # group 0 below 2^53, group 1 passes it

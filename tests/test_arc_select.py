@@ -2,8 +2,9 @@
 (selection network, and the padded Batcher sort it replaces), and arc_keys — checked on the CPU
 with a stand-alone probe (tests/arc_select_probe.cpp: its own main, only that header, no HIP and
 no libecc): every 0/1
-input (2^16 and 2^20), 10^5 tie-heavy random key sets per circle against std::sort, and arc_keys
-against the count form of arc_streak including the undecidable return.
+input (2^16 and 2^20), 10^5 tie-heavy random key sets per circle against std::sort, arc_keys
+against the count form of arc_streak including the undecidable return, and the maps to clamped keys
+(arc_clamp_value, arc_clamp_rel) over the int64 edges against 128-bit arithmetic.
 """
 import subprocess
 from pathlib import Path

@@ -8,7 +8,16 @@ import numpy as np
 import pytest
 
 CTX, XY, CNT, INIT, CENT, LAB, SIZES, ITERS = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000, 0x6000, 0x7000, 0x8000
-NO_CFG = object()
+
+
+class _NoCfg:
+    """Stands for a NULL cfg pointer; its repr is part of a test id, so it must not hold an address."""
+
+    def __repr__(self):
+        return "NULL"
+
+
+NO_CFG = _NoCfg()
 
 
 def call(ecc, ctx=CTX, xy=XY, n_segs=2, stride=64, counts=CNT, k=16, max_iters=5, cfg=None, init=INIT, cent=CENT,

@@ -73,6 +73,18 @@ def test_arc_lambda(ecc, orc, tmp_path, name):
         assert len(ref["corners"][0]) == 0  # no detection before the first slice callback (:878, :926)
 
 
+def test_arc_lambda_int64_extremes(ecc, tmp_path):
+    """The reference's own verdicts on the tests that arc_path_cases.future_sae plants in slice 0 on
+    surfaces of 2^62, INT64_MAX - 1 and INT64_MAX (at PATCH) and of INT64_MIN and INT64_MIN + 1 (at
+    PATCH_B): INT64_MAX is the newest value of a circle, and values that are one double tie (the
+    fourth probe of each patch, which int64 order would make a corner)."""
+    _, ref = _ref_arc_case(ecc, tmp_path, "future_sae")
+    first = {tuple(p) for p in ref["corners"][0]}
+    centres = rc.ap.ALONE + rc.ap.SHARED
+    for origin, want in ((rc.PATCH, [1, 1, 1, 0, 1, 0, 1, 1]), (rc.PATCH_B, [1, 1, 1, 0, 0, 0, 0, 0])):
+        assert [int((origin[0] + cx, origin[1] + cy) in first) for cx, cy in centres] == want, origin
+
+
 def test_arc_lambda_border_break_cuts_slices(ecc, orc, tmp_path):
     """The planted border events end their slices' tests: the reference's lists differ from the
     border-free stream's exactly in those slices, and only after the planted position."""
