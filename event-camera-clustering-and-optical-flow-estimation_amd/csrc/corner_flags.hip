@@ -1,37 +1,58 @@
 // Corner detection, stage 6: the corner flags in event order, and for the fused detect + NMS
 // calls each slice's NMS candidate list (pipeline: corners.hip).
 #include "corner_common.hpp"
+#include "flag_decode.hpp"
 
 namespace {
 
 // 6. Corner flags in event order: one workgroup per slice.  Event i of slice s (group g, slice j
 // of the group) is a corner iff its (slice, pixel) pair's bit is set in the result words of its
 // (g, tile) item.  The workgroup first stages slice j's 196-bit segment of every tile's result
-// vector in LDS (7 words per tile), so each event's lookup is an LDS read; every flag is then
+// vector in LDS (7 words per tile), so each event's lookup is an LDS read (word and bit from
+// flag_decode.hpp, for every event alike: no branch and no wait per event); every flag is then
 // written, 0 or 1, four per lane and store.  The per-event eligibility of the reference loop: the
 // first-detect rule (Q15) and, in ref_compat mode (Q11), "before the slice's first border event";
 // corner pairs are never border pixels.
 #ifndef ECC_FLAG_THREADS
 #define ECC_FLAG_THREADS 256
 #endif
-constexpr int kFlagThreads = ECC_FLAG_THREADS;  // 256: every slice's workgroup resident at once (8 per CU)
+constexpr int kFlagThreads = ECC_FLAG_THREADS;  // 256: every slice's workgroup resident at once (5 per CU)
 #ifndef ECC_FLAG_QUADS
 #define ECC_FLAG_QUADS 8
 #endif
 constexpr int kFlagQuads = ECC_FLAG_QUADS;  // 4-event quads a lane has in flight per batch
 constexpr int kFlagBatch = kFlagQuads * kFlagThreads;  // quads per batch
 
-// kStaged: bit lp of tile in the LDS segments; otherwise (sensors whose segments exceed the
-// LDS) straight from the group's result words.
+// Quads whose LDS reads are issued together, before the first of them is consumed (all 8 of a
+// batch would take 124 VGPRs: four workgroups per CU, and the slices no longer resident at once).
+#ifndef ECC_FLAG_GROUP
+#define ECC_FLAG_GROUP 4
+#endif
+constexpr int kFlagGroup = ECC_FLAG_GROUP;
+static_assert(kFlagQuads % kFlagGroup == 0, "a batch is whole read groups");
+static_assert(kFlagTile == (uint32_t)kTile && kFlagSegWords == (uint32_t)kSegWords, "flag_decode.hpp's tile");
+
+// kStaged: word `w` of the slice's result segments from LDS; otherwise (sensors whose segments
+// exceed the LDS) straight from the group's result words.  w <= last_word: inside both.
 template <bool kStaged>
-__device__ __forceinline__ uint32_t corner_bit(uint32_t v, const CornerGeom &g, const uint32_t *sb,
-                                               const uint32_t *__restrict__ rg, int j) {
-    const int x = ecc::xy_x(v), y = ecc::xy_y(v);
-    if (x >= g.W || y >= g.H) return 0u;
-    const int tile = (y / kTile) * g.tiles_x + x / kTile;
-    const int lp = (y % kTile) * kTile + x % kTile;
-    if (kStaged) return (sb[tile * kSegWords + (lp >> 5)] >> (lp & 31)) & 1u;
-    return (rg[(int64_t)tile * kSegWords + (lp >> 5)] >> (lp & 31)) & 1u;
+__device__ __forceinline__ uint32_t seg_word(uint32_t w, const uint32_t *sb, const uint32_t *__restrict__ rg) {
+    return kStaged ? sb[w] : rg[w];
+}
+
+// One event's flag (the scalar tails).  Nothing is under a branch: the word index is clamped
+// (flag_slot), and an event off the sensor masks the bit it read.
+template <bool kStaged>
+__device__ __forceinline__ uint32_t corner_bit(uint32_t v, const CornerGeom &g, uint32_t last_word, const uint32_t *sb,
+                                               const uint32_t *__restrict__ rg) {
+    const uint32_t x = (uint32_t)ecc::xy_x(v), y = (uint32_t)ecc::xy_y(v);
+    const FlagSlot sl = flag_slot(x, y, (uint32_t)g.tiles_x, last_word);
+    return (seg_word<kStaged>(sl.word, sb, rg) >> sl.bit) & flag_on_sensor(x, y, (uint32_t)g.W, (uint32_t)g.H);
+}
+
+// 0x01 in byte k for k < r (r of any sign): the events of a quad before an end r events away
+__device__ __forceinline__ uint32_t first_bytes(int r) {
+    const int rc = min(max(r, 0), 4);
+    return rc >= 4 ? 0x01010101u : (0x01010101u & ((1u << (8 * (rc & 3))) - 1u));
 }
 
 // kCand (ecc_fast_detect_nms): the pass also writes each slice's NMS candidate list — the
@@ -40,7 +61,8 @@ __device__ __forceinline__ uint32_t corner_bit(uint32_t v, const CornerGeom &g, 
 // slices of at most kFlagCandMax events, a multiple of 4, with 4-B aligned flags: every slice then
 // runs in quads).
 // 256-lane workgroups, one per slice, so that all 1221 slices of the bench batch are resident at
-// once (eight per CU; 512-lane ones left a second round of 197 workgroups as a tail).  A slice's
+// once (five per CU at the kernel's 90 VGPRs, which 1221 / 256 = 4.8 needs; 512-lane ones left a
+// second round of 197 workgroups as a tail).  A slice's
 // quads are taken in batches of kFlagQuads per lane: the first batch's loads are issued before
 // the staging of the result segments, so the two latencies overlap.
 template <bool kStaged, bool kCand>
@@ -53,7 +75,7 @@ flags_event_kernel(const uint32_t *__restrict__ xy, CornerGeom g, const uint32_t
     const int64_t s = blockIdx.x;
     const int64_t lo = s * g.S;
     const int len = (int)((lo + g.S < g.n ? lo + g.S : g.n) - lo);
-    const int j = (int)(s % kGroup);
+    const uint32_t last_word = (uint32_t)(g.n_tiles * kSegWords - 1);  // of the slice's segments
     // events [0, live_end) of the slice can be corners
     const int live_end = s < g.first_detect ? 0 : (g.border_mode == 1 ? min(len, max(first_border[s], 0)) : len);
     const uint32_t *rg = res + s * g.seg_stride;  // slice s's segment of every tile (16-B aligned)
@@ -97,11 +119,15 @@ flags_event_kernel(const uint32_t *__restrict__ xy, CornerGeom g, const uint32_t
         }
     }
     __syncthreads();
-    auto quad_flags = [&](int i, const uint4 v) {
-        return corner_bit<kStaged>(v.x, g, sb, rg, j) | (i + 1 < live_end ? corner_bit<kStaged>(v.y, g, sb, rg, j) << 8 : 0u) |
-               (i + 2 < live_end ? corner_bit<kStaged>(v.z, g, sb, rg, j) << 16 : 0u) |
-               (i + 3 < live_end ? corner_bit<kStaged>(v.w, g, sb, rg, j) << 24 : 0u);
-    };
+    // No event is under a branch.  Every slot of a batch is decoded and looked up, whatever it
+    // holds: a quad past the slice's quads loads zeros (pixel (0, 0): in bounds), an event off the
+    // sensor reads a clamped word; what must not count is masked out of the packed quad word
+    // afterwards: the on-sensor bytes, and the bytes before `live_q` (live_end, held to the
+    // slice's whole quads).  The flag store goes through a buffer view of the slice's whole quads
+    // (dropped past them; when `vec`, flags + lo is 4-B aligned).  A read group's LDS reads are
+    // all issued before the first is consumed.
+    const int live_q = min(live_end, 4 * n4);
+    const __amdgpu_buffer_rsrc_t vf = ecc::buffer_view(flags + lo, (uint32_t)n4 * 4u);
     const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     int base = 0;  // candidates written so far (uniform)
     uint32_t *dst = cand + lo;
@@ -110,11 +136,33 @@ flags_event_kernel(const uint32_t *__restrict__ xy, CornerGeom g, const uint32_t
         uint32_t f[kFlagQuads];
         int pfx[kFlagQuads];
 #pragma unroll
+        for (int u0 = 0; u0 < kFlagQuads; u0 += kFlagGroup) {
+            uint32_t wd[kFlagGroup][4], sh[kFlagGroup], ok[kFlagGroup];  // words; bit numbers, on-sensor: a byte each
+#pragma unroll
+            for (int u = 0; u < kFlagGroup; ++u) {
+                const uint32_t ev[4] = {pre[u0 + u].x, pre[u0 + u].y, pre[u0 + u].z, pre[u0 + u].w};
+                sh[u] = ok[u] = 0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t x = (uint32_t)ecc::xy_x(ev[k]), y = (uint32_t)ecc::xy_y(ev[k]);
+                    const FlagSlot sl = flag_slot(x, y, (uint32_t)g.tiles_x, last_word);
+                    wd[u][k] = seg_word<kStaged>(sl.word, sb, rg);
+                    sh[u] |= sl.bit << (8 * k);
+                    ok[u] |= flag_on_sensor(x, y, (uint32_t)g.W, (uint32_t)g.H) << (8 * k);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kFlagGroup; ++u) {
+                const int i = 4 * (q0 + (u0 + u) * kFlagThreads + (int)threadIdx.x);
+                uint32_t bits = 0u;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) bits |= ((wd[u][k] >> ((sh[u] >> (8 * k)) & 31u)) & 1u) << (8 * k);
+                f[u0 + u] = bits & ok[u] & first_bytes(live_q - i);
+                ecc::buffer_store_u32(f[u0 + u], vf, threadIdx.x * 4u, (uint32_t)(q0 + (u0 + u) * kFlagThreads) * 4u);
+            }
+        }
+#pragma unroll
         for (int u = 0; u < kFlagQuads; ++u) {
-            const int q = q0 + u * kFlagThreads + (int)threadIdx.x;
-            const int i = 4 * q;
-            f[u] = (q < n4 && i < live_end) ? quad_flags(i, pre[u]) : 0u;
-            if (q < n4) *reinterpret_cast<uint32_t *>(flags + lo + i) = f[u];
             if constexpr (kCand) {
                 // quad u of lane tid holds events 4 (q0 + u * T + tid) .. + 3: event order is u,
                 // then lane; a quad has <= 4 flags, so three ballots give each lane its prefix
@@ -149,7 +197,7 @@ flags_event_kernel(const uint32_t *__restrict__ xy, CornerGeom g, const uint32_t
         if (threadIdx.x == 0) {
             for (int i = 4 * n4; i < len; ++i) {  // the batch's last < 4 events, in order
                 const uint32_t v = xy[lo + i];
-                const uint32_t fb = i < live_end ? corner_bit<kStaged>(v, g, sb, rg, j) : 0u;
+                const uint32_t fb = corner_bit<kStaged>(v, g, last_word, sb, rg) & (i < live_end ? 1u : 0u);
                 flags[lo + i] = (uint8_t)fb;
                 if (fb) dst[base++] = v;
             }
@@ -157,7 +205,7 @@ flags_event_kernel(const uint32_t *__restrict__ xy, CornerGeom g, const uint32_t
         }
     } else {
         for (int i = 4 * n4 + threadIdx.x; i < len; i += kFlagThreads)  // last < 4 events, or unaligned slices
-            flags[lo + i] = (uint8_t)(i < live_end ? corner_bit<kStaged>(xy[lo + i], g, sb, rg, j) : 0u);
+            flags[lo + i] = (uint8_t)(corner_bit<kStaged>(xy[lo + i], g, last_word, sb, rg) & (i < live_end ? 1u : 0u));
     }
 }
 
