@@ -1,7 +1,8 @@
-// The arc test's sorting and selection helpers and its maps to clamped keys, shared by arc_kernel
-// and arc_dense_kernel.  Plain C++: compiles for the host too (tests/arc_select_probe.cpp runs
-// every 0/1 input through the networks there, checks arc_keys against arc_streak's count form and
-// the clamps over the int64 edges).
+// The arc test's sorting and selection helpers, its maps to clamped keys and the index arithmetic
+// of arc_kernel's compact value lists, shared by arc_kernel and arc_dense_kernel.  Plain C++:
+// compiles for the host too (tests/arc_select_probe.cpp runs every 0/1 input through the networks
+// there, checks arc_keys against arc_streak's count form and the clamps over the int64 edges;
+// tests/arc_lookup_probe.cpp runs the index arithmetic over every slice and the edge offsets).
 #pragma once
 #include <cstdint>
 
@@ -159,6 +160,22 @@ ECC_SEL_HD int arc_keys(uint32_t (&keys)[N], bool ties_exact) {
         }
     }
     return ok ? 1 : 0;
+}
+
+// ---- the compact value list's index arithmetic (arc_kernel) -----------------------------------
+// slices 0 .. j (j <= 31: 2u << 31 is 0 in 32 bits, so j = 31 gives all ones without a select)
+ECC_SEL_HD uint32_t arc_below_mask(int j) { return (2u << j) - 1u; }
+
+// A window pixel keeps its clamped B_g slot followed by the values of the slices in `mask`,
+// ascending j, from byte `off_bytes` of the value array (a multiple of 4).  The byte an event of
+// slice j reads: the B_g slot when no slice <= j touched the pixel, else the value of the latest
+// such slice.  The offset is kept in bytes so that the device forms the address with an AND, a
+// population count and one shift-and-add (a word offset cost a second shift per lookup).
+ECC_SEL_HD uint32_t arc_value_byte_below(uint32_t mask, uint32_t below, uint32_t off_bytes) {
+    return ((uint32_t)__builtin_popcount(mask & below) << 2) + off_bytes;
+}
+ECC_SEL_HD uint32_t arc_value_byte(uint32_t mask, int j, uint32_t off_bytes) {
+    return arc_value_byte_below(mask, arc_below_mask(j), off_bytes);
 }
 
 // ---- the maps from surface values to clamped keys ---------------------------------------------

@@ -9,10 +9,10 @@ namespace {
 
 constexpr int kArcThreads = 512;  // 8 waves: one lane per window pixel (484) when staging
 
-__constant__ int8_t c3dy[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
-__constant__ int8_t c3dx[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
-__constant__ int8_t c4dy[20] = {0, 1, 2, 3, 4, 4, 4, 3, 2, 1, 0, -1, -2, -3, -4, -4, -4, -3, -2, -1};
-__constant__ int8_t c4dx[20] = {4, 4, 3, 2, 1, 0, -1, -2, -3, -4, -4, -4, -3, -2, -1, 0, 1, 2, 3, 4};
+__constant__ constexpr int8_t c3dy[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+__constant__ constexpr int8_t c3dx[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
+__constant__ constexpr int8_t c4dy[20] = {0, 1, 2, 3, 4, 4, 4, 3, 2, 1, 0, -1, -2, -3, -4, -4, -4, -3, -2, -1};
+__constant__ constexpr int8_t c4dx[20] = {4, 4, 3, 2, 1, 0, -1, -2, -3, -4, -4, -4, -3, -2, -1, 0, 1, 2, 3, 4};
 
 // arc_streak (the count form, used by the exact tests), sort_desc, the selection networks and
 // arc_keys (the fast test on clamped 32-bit keys) are in arc_select.hpp, which the host compiles too.
@@ -95,8 +95,8 @@ __device__ __forceinline__ bool clamp_mixed(const int64_t *wc0, const int32_t *w
 // (arc_clamp_value and arc_clamp_rel, the maps to clamped keys, are in arc_select.hpp: the host runs them
 // over the int64 edges)
 
-// slices 0 .. j (j <= 31: 2u << 31 is 0 in 32 bits, so j = 31 gives all ones without a select)
-__device__ __forceinline__ uint32_t below_mask(int j) { return (2u << j) - 1u; }
+// slices 0 .. j (arc_select.hpp: the host checks it with the compact list's index arithmetic)
+__device__ __forceinline__ uint32_t below_mask(int j) { return arc_below_mask(j); }
 
 // Clamped value at window pixel wp for slice j (fast path).
 __device__ __forceinline__ uint32_t win_value(const ArcLds &L, int wp, uint32_t below) {
@@ -403,9 +403,9 @@ __device__ __forceinline__ void arc_dense_item(ArcLds &L, int64_t item, const in
 
 // ---- compact window values (the common case) -------------------------------------------------
 // Window pixel wp keeps its clamped B_g followed by the values of the slices that touched it,
-// ascending j, at vals[pix[wp].off ...]; the value an event of slice j sees is
-// vals[off + popc(mask & ((2 << j) - 1))] — index off (the B_g slot) when no slice <= j touched
-// the pixel, so a lookup is one 8-B pixel read and one value read, no select.  ~34 KB of LDS
+// ascending j, from byte pix[wp].off of vals; the value an event of slice j sees is the word at
+// byte off + 4 * popc(mask & ((2 << j) - 1)) (arc_value_byte) — the B_g slot when no slice <= j
+// touched the pixel, so a lookup is one 8-B pixel read and one value read, no select.  ~34 KB of LDS
 // instead of the dense planes' ~80 KB: four 8-wave workgroups per CU.  Windows with more than
 // kValCap values go to the overflow list (arc_dense_kernel).
 #ifndef ECC_ARC_VALCAP
@@ -415,12 +415,17 @@ constexpr int kValCap = ECC_ARC_VALCAP;
 
 struct PixInfo {
     uint32_t mask;  // slices of the group that touched the pixel
-    uint32_t off;   // its B_g slot in vals[], the slice values follow
+    uint32_t off;   // its B_g slot in vals[], in BYTES (4 * the word index); the slice values follow
 };
 
+// pix stands first: a task's circle pixels are then all read off ONE address register, the
+// record of the window pixel four rows up and four columns left of the task's (circle_base),
+// with each pixel's displacement in the read's offset field.  ds_read2_b64's two offsets count
+// 8-B units up to 255; in the middle of the struct the compiler rounded the address down to
+// what those fields reach and needed five registers per circle-3 trip for it.
 struct SparseLds {
-    uint32_t vals[kValCap + kWinPix];   // 17.9 KiB: the pairs + one B_g slot per window pixel
     PixInfo pix[kWinPix];               // 3.8 KiB
+    uint32_t vals[kValCap + kWinPix];   // 17.9 KiB: the pairs + one B_g slot per window pixel
     uint32_t res[kPairWords];
     uint16_t tasks[kValCap];  // the tile's eligible pairs (j << 9 | window pixel): at most the window's pairs
     uint16_t q4[kQ4Cap];
@@ -433,10 +438,33 @@ struct SparseLds {
 // Branch-free by layout: one 8-B pixel read and one value read (a conditional read compiles to
 // an exec-mask branch per circle pixel: scalar-unit bookkeeping, serialised LDS round trips).
 static_assert(sizeof(PixInfo) == 8, "one 8-B LDS read per pixel");
-__device__ __forceinline__ uint32_t sparse_value(const SparseLds &L, int wp, uint32_t below) {
-    const uint2 p = reinterpret_cast<const uint2 *>(L.pix)[wp];  // {mask, off}
-    return L.vals[p.y + __popc(p.x & below)];
+__device__ __forceinline__ uint32_t sparse_value(const SparseLds &L, const uint2 *pix, int d, uint32_t below) {
+    const uint2 p = pix[d];  // {mask, off in bytes}
+    return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(L.vals) +
+                                               arc_value_byte_below(p.x, below, p.y));
 }
+
+// The circles' pixel reads are relative to the window pixel kHalo rows up and kHalo columns left
+// of the task's: displacement (dy + kHalo) * kWin + dx + kHalo, never negative, and small
+// enough for the paired 8-B read's offset field whatever the task pixel.
+// The byte offset passes through an empty asm so that it stays one value in one register: left
+// to itself the compiler folds the constant back into the displacements, half of them negative
+// again, and forms a register per negative one (seven adds per circle-3 trip).
+__device__ __forceinline__ const uint2 *circle_base(const SparseLds &L, int wp0) {
+    uint32_t b = (uint32_t)(wp0 - kHalo * kWin - kHalo) * (uint32_t)sizeof(PixInfo);
+    asm("" : "+v"(b));
+    return reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(L.pix) + b);
+}
+constexpr int circle_disp(int dy, int dx) { return (dy + kHalo) * kWin + dx + kHalo; }
+template <int N>
+constexpr bool circle_disps_fit(const int8_t (&dy)[N], const int8_t (&dx)[N]) {
+    for (int k = 0; k < N; ++k)
+        if (circle_disp(dy[k], dx[k]) < 0 || circle_disp(dy[k], dx[k]) > 255) return false;
+    return true;
+}
+static_assert(circle_disps_fit(c3dy, c3dx) && circle_disps_fit(c4dy, c4dx),
+              "every circle pixel within ds_read2_b64's offset field (8-B units, 8 bits: below 2040 B)");
+static_assert(offsetof(SparseLds, pix) == 0, "the circle base is 8 * task pixel less a constant: no struct offset to add");
 
 #ifndef ECC_ARC_SKIP_OVF
 #define ECC_ARC_SKIP_OVF 0  // timing experiments only (wrong results): 1 = no overflow loads past the first line
@@ -597,7 +625,7 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
     }
     if (win_lane) {
         const uint32_t bcv = arc_clamp_value(bq, Lt, kVMax, narrow, inside, &L.exact_only);  // above the range: the exact kernel
-        reinterpret_cast<uint2 *>(L.pix)[wp] = make_uint2(mk_w, (uint32_t)off);
+        reinterpret_cast<uint2 *>(L.pix)[wp] = make_uint2(mk_w, 4u * (uint32_t)off);  // bytes; dst keeps the word offset
         uint32_t *dst = L.vals + off;
         dst[0] = bcv;
         if (p > 0) dst[1] = pre.rec.x;
@@ -644,8 +672,9 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
         const int wp0 = pi & 511;
         const uint32_t below = below_mask(pi >> 9);
         uint32_t k3[16];
+        const uint2 *pb = circle_base(L, wp0);
 #pragma unroll
-        for (int k = 0; k < 16; ++k) k3[k] = (sparse_value(L, wp0 + c3dy[k] * kWin + c3dx[k], below) << 5) | k;
+        for (int k = 0; k < 16; ++k) k3[k] = (sparse_value(L, pb, circle_disp(c3dy[k], c3dx[k]), below) << 5) | k;
         const int r3 = arc_keys<16, 5, 3, 6>(k3, ties_exact);
         if (r3 > 0) {
             const int qi = atomicAdd(&L.q4n, 1);
@@ -673,8 +702,9 @@ __device__ __forceinline__ void arc_item(SparseLds &L, int64_t item, const ArcPr
         const int j = pt >> 9, wp0 = pt & 511;
         const uint32_t below = below_mask(j);
         uint32_t k4[20];
+        const uint2 *pb = circle_base(L, wp0);
 #pragma unroll
-        for (int k = 0; k < 20; ++k) k4[k] = (sparse_value(L, wp0 + c4dy[k] * kWin + c4dx[k], below) << 5) | k;
+        for (int k = 0; k < 20; ++k) k4[k] = (sparse_value(L, pb, circle_disp(c4dy[k], c4dx[k]), below) << 5) | k;
         const int r4 = arc_keys<20, 5, 4, 8>(k4, ties_exact);
         if (r4 > 0) {  // the pair's bit: slice j, tile pixel (wp0's row and column less the halo)
             const int pi = j * kTilePix + (wp0 / kWin - kHalo) * kTile + (wp0 % kWin - kHalo);
