@@ -20,8 +20,10 @@
 // parallel compaction kernel (256 lanes per slice) first lists each slice's flagged events in
 // event order; one wave per slice then takes them 64 at a time, and within a chunk the kept ones
 // are found by a scalar loop over the surviving lanes (each kept lane's centre is broadcast and
-// kills the later lanes it overlaps).  ~2 KiB of LDS per slice, so many slices run per CU.
+// kills the later lanes it overlaps).  ~4 KiB of LDS per slice at the bench's sizes (grid and
+// kept list), so many slices run per CU.
 #include "ecc_internal.hpp"
+#include "nms_cell.hpp"
 
 namespace {
 
@@ -146,9 +148,7 @@ nms_kernel(const uint32_t *__restrict__ xy, const uint8_t *__restrict__ flags, i
 }
 
 
-constexpr int kGridThreads = 64;
 constexpr int kGridMaxCells = 16384;  // 64 KiB of LDS
-constexpr uint32_t kNoCentre = 0xffffffffu;
 
 __device__ __forceinline__ bool near_centre(uint32_t a, uint32_t b, int reach) {
     return abs(ecc::xy_x(a) - ecc::xy_x(b)) <= reach && abs(ecc::xy_y(a) - ecc::xy_y(b)) <= reach;
@@ -214,65 +214,170 @@ nms_compact_kernel(const uint32_t *__restrict__ xy, const uint8_t *__restrict__ 
     if (tid == 0) n_cand[s] = run;
 }
 
-// nms_greedy_kernel: one wave per slice over its candidate list (the next 64 candidates are
-// requested before the current 64 are decided); the kept-centre grid as in nms_grid_kernel.
-__global__ void __launch_bounds__(kGridThreads)
-nms_greedy_kernel(const uint32_t *__restrict__ cand, const int32_t *__restrict__ n_cand, int S, int W, int H,
-                  int half, int gw, int gh, int cap, ecc_corner *__restrict__ out, int32_t *__restrict__ out_count,
-                  int32_t *__restrict__ err) {
-    extern __shared__ uint32_t grid[];  // [gh][gw] kept centre per cell
-    const int lane = threadIdx.x;
+// ---- the greedy pass over the candidate lists ---------------------------------------------------
+// One workgroup per slice takes its list in batches of 64 x waves (the next batch is requested
+// before this one is decided); the kept-centre grid as described at the top of the file.
+// Build switches (measured alone and together, profiles/nms_batch_ab.txt):
+//   ECC_NMS_WAVES  waves per slice.  1: a batch is one chunk of 64, probed and decided by the one
+//                  wave.  More: every lane probes one candidate of the batch against the grid as it
+//                  stood before the batch, the survivors are listed in candidate order, and wave 0
+//                  alone runs the greedy chunk code over that list.  On the bench stream a slice's
+//                  first 256 candidates meet an empty grid and all survive, so 2, 4 and 8 waves
+//                  measured slower than one: 1 is the default.
+//   ECC_NMS_LEAN   1: cell by multiply-high, nine unguarded probes and the keep loop's reach test
+//                  as one unsigned compare (nms_cell.hpp), the first batch's loads issued beside
+//                  the n_cand load, kept centres listed in LDS and written out after the loop.
+//                  0: the divisions, guarded probes and in-loop stores of the pass as it was.
+#ifndef ECC_NMS_WAVES
+#define ECC_NMS_WAVES 1
+#endif
+#ifndef ECC_NMS_LEAN
+#define ECC_NMS_LEAN 1
+#endif
+constexpr int kNmsWaves = ECC_NMS_WAVES;
+constexpr bool kNmsLean = ECC_NMS_LEAN != 0;
+static_assert(kNmsWaves >= 1 && kNmsWaves <= 16, "ECC_NMS_WAVES: 1 .. 16");
+
+template <bool LEAN>
+__device__ __forceinline__ bool cell_free(const uint32_t *grid, int c0, int pw, uint32_t v, int reach) {
+    uint32_t kc[9];
+#pragma unroll
+    for (int d = 0; d < 9; ++d) kc[d] = grid[c0 + (d / 3) * pw + d % 3];
+    if constexpr (LEAN) {
+        const NmsKey k = nms_key(v, reach);
+        uint32_t nearest = UINT32_MAX;  // an empty cell is out of every reach (nms_cell.hpp)
+#pragma unroll
+        for (int d = 0; d < 9; ++d) nearest = min(nearest, nms_span(k, kc[d]));
+        return nearest > 2u * (uint32_t)reach;
+    } else {
+        bool free_ = true;
+#pragma unroll
+        for (int d = 0; d < 9; ++d) free_ &= !(kc[d] != kNoCentre && near_centre(kc[d], v, reach));
+        return free_;
+    }
+}
+
+// One workgroup of WAVES waves per slice.  LDS: the padded grid, then (WAVES > 1) the waves'
+// survivor lists of 64 {xy, cell} pairs and their counts, then (LDS_OUT) the kept centres in rank
+// order, kl <= cap of them (at most one per cell, so gw * gh bound the list), and one word for the
+// kept count.  A candidate that the batch probe drops lies within reach of a centre that is final;
+// the greedy pass drops it whatever follows and a dropped candidate influences nobody, so wave 0's
+// pass over the survivors in unchanged order keeps the same centres at the same ranks.
+template <int WAVES, bool LEAN, bool LDS_OUT>
+__global__ void __launch_bounds__(64 * WAVES)
+nms_batch_kernel(const uint32_t *__restrict__ cand, const int32_t *__restrict__ n_cand, int64_t n, int S, int W, int H,
+                 int half, int gw, int gh, int cap, int kl, uint32_t cell_mul, uint32_t cell_sh,
+                 ecc_corner *__restrict__ out, int32_t *__restrict__ out_count, int32_t *__restrict__ err) {
+    constexpr int NT = 64 * WAVES;
+    extern __shared__ uint32_t grid[];  // [gh + 2][gw + 2] kept centre per cell
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t s = blockIdx.x;
-    const uint32_t *c = cand + s * (int64_t)S;
-    const int total = n_cand[s];
-    const int cs = 2 * half + 1, reach = 2 * half;
-    const int pw = gw + 2;  // one border cell on every side: the 3x3 probes need no bounds checks
-    for (int i = lane; i < pw * (gh + 2); i += kGridThreads) grid[i] = kNoCentre;
+    const int64_t lo = s * (int64_t)S;
+    const int len = (int)((lo + S < n ? lo + S : n) - lo);  // >= 1: the slice exists
+    const uint32_t *c = cand + lo;
+    const int cs = 2 * half + 1, reach = LEAN ? nms_reach(half) : 2 * half;
+    const int pw = gw + 2;
+    const int cells = pw * (gh + 2);
+    uint2 *surv = reinterpret_cast<uint2 *>(grid + ((cells + 1) & ~1));  // [WAVES][64]
+    uint32_t *wcnt = reinterpret_cast<uint32_t *>(surv + (WAVES > 1 ? NT : 0));  // [WAVES]
+    uint32_t *keptl = wcnt + (WAVES > 1 ? WAVES : 0);                            // [kl]
+    uint32_t *n_kept_all = keptl + (LDS_OUT ? kl : 0);
+    // LEAN: the slice owns len slots of cand, so its first batch is read (clamped) without waiting
+    // for its count
+    uint32_t nxt = 0u;
+    if constexpr (LEAN) nxt = c[min(tid, len - 1)];
+    const int total = min(max(n_cand[s], 0), len);
+    if constexpr (!LEAN) nxt = tid < total ? c[tid] : 0u;
+    for (int i = tid; i < cells; i += NT) grid[i] = kNoCentre;
     const uint64_t lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    int n_kept = 0;
+    int n_kept = 0;  // wave 0's
     bool overflow = false, bad_input = false;
-    uint32_t nxt = lane < total ? c[lane] : 0u;
     __syncthreads();
-    for (int p0 = 0; p0 < total; p0 += kGridThreads) {
+    // wave 0 (wave-uniform): the greedy step over 64 candidates v at cells c0, `alive` those that no
+    // earlier kept centre reaches
+    auto resolve = [&](uint32_t v, int c0, bool alive) {
+        uint64_t am = __ballot(alive), keepm = 0;
+        const NmsKey key = nms_key(v, reach);
+        while (am) {  // each step keeps the first surviving lane
+            const int i0 = __ffsll((unsigned long long)am) - 1;
+            keepm |= 1ull << i0;
+            am &= am - 1;
+            const uint32_t vi = (uint32_t)__builtin_amdgcn_readlane((int)v, i0);
+            // (LEAN: am holds lanes above i0 only, so the lanes need not say where they are)
+            if constexpr (LEAN) am &= ~__ballot(nms_span(key, vi) <= 2u * (uint32_t)reach);
+            else am &= ~__ballot(lane > i0 && near_centre(vi, v, reach));
+        }
+        if ((keepm >> lane) & 1ull) {
+            const int rank = n_kept + __popcll(keepm & lt_mask);
+            grid[c0 + pw + 1] = v;
+            if constexpr (LDS_OUT) {
+                if (rank < kl) keptl[rank] = v;
+                if (rank >= cap) overflow = true;
+            } else {
+                if (rank < cap) out[s * (int64_t)cap + rank] = ecc_corner{ecc::xy_x(v), ecc::xy_y(v), rank};
+                else overflow = true;
+            }
+        }
+        n_kept += __popcll(keepm);
+    };
+    for (int b0 = 0; b0 < total; b0 += NT) {
         uint32_t v = nxt;
-        const bool have = p0 + lane < total;
-        nxt = (p0 + kGridThreads + lane < total) ? c[p0 + kGridThreads + lane] : 0u;
+        const bool have = b0 + tid < total;
+        if constexpr (LEAN) nxt = c[min(b0 + NT + tid, len - 1)];
+        else nxt = (b0 + NT + tid < total) ? c[b0 + NT + tid] : 0u;
         int x = ecc::xy_x(v), y = ecc::xy_y(v);
         const bool outside = have && (x >= W || y >= H);
         if (outside) bad_input = true;  // skipped and reported (ecc_corner_nms_status)
         const bool valid = have && !outside;
         if (!valid) { v = 0u; x = 0; y = 0; }
-        const int cx = x / cs, cy = y / cs;
-        bool alive = valid;
+        const int cx = LEAN ? (int)magic_quot((uint32_t)x, cell_mul, cell_sh) : x / cs;
+        const int cy = LEAN ? (int)magic_quot((uint32_t)y, cell_mul, cell_sh) : y / cs;
         const int c0 = cy * pw + cx;  // padded cell (cx, cy) - (1, 1)
-        uint32_t kc[9];
+        const bool alive = valid && cell_free<LEAN>(grid, c0, pw, v, reach);
+        if constexpr (WAVES == 1) {
+            resolve(v, c0, alive);
+        } else {
+            const uint64_t am = __ballot(alive);
+            if (alive) surv[wave * 64 + __popcll(am & lt_mask)] = make_uint2(v, (uint32_t)c0);
+            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(am);
+            __syncthreads();
+            if (wave == 0) {
+                int first[WAVES + 1];  // survivor i of the batch is wave w's (i - first[w])-th
+                first[0] = 0;
 #pragma unroll
-        for (int d = 0; d < 9; ++d) kc[d] = grid[c0 + (d / 3) * pw + d % 3];
+                for (int w = 0; w < WAVES; ++w) first[w + 1] = first[w] + (int)wcnt[w];
+                const int tot = first[WAVES];
+                for (int q0 = 0; q0 < tot; q0 += 64) {
+                    const int i = q0 + lane;
+                    int src = i;
 #pragma unroll
-        for (int d = 0; d < 9; ++d) alive &= !(kc[d] != kNoCentre && near_centre(kc[d], v, reach));
-        uint64_t am = __ballot(alive), keepm = 0;
-        while (am) {  // wave-uniform: each step keeps the first surviving lane
-            const int i0 = __ffsll((unsigned long long)am) - 1;
-            keepm |= 1ull << i0;
-            am &= am - 1;
-            const uint32_t vi = (uint32_t)__builtin_amdgcn_readlane((int)v, i0);
-            am &= ~__ballot(lane > i0 && near_centre(vi, v, reach));
+                    for (int w = 1; w < WAVES; ++w) src += i >= first[w] ? 64 - (first[w] - first[w - 1]) : 0;
+                    const bool have2 = i < tot;
+                    const uint2 e = surv[have2 ? src : 0];
+                    // the chunk before this one may have kept a centre within reach
+                    const bool alive2 = have2 && (q0 == 0 || cell_free<LEAN>(grid, (int)e.y, pw, e.x, reach));
+                    resolve(e.x, (int)e.y, alive2);
+                }
+            }
         }
-        if ((keepm >> lane) & 1ull) {
-            const int rank = n_kept + __popcll(keepm & lt_mask);
-            grid[c0 + pw + 1] = v;
-            if (rank < cap) out[s * (int64_t)cap + rank] = ecc_corner{x, y, rank};
-            else overflow = true;
-        }
-        n_kept += __popcll(keepm);
         __syncthreads();
     }
+    if (__any(bad_input) && lane == 0) atomicOr(err, 2);
+    if constexpr (LDS_OUT) {
+        if (tid == 0) *n_kept_all = (uint32_t)n_kept;
+        __syncthreads();
+        const int m = min(min((int)*n_kept_all, cap), kl);
+        for (int r = tid; r < m; r += NT) {
+            const uint32_t v = keptl[r];
+            out[s * (int64_t)cap + r] = ecc_corner{ecc::xy_x(v), ecc::xy_y(v), r};
+        }
+    }
+    if (wave != 0) return;
     overflow = __any(overflow);
-    bad_input = __any(bad_input);
     if (lane == 0) {
         out_count[s] = n_kept < cap ? n_kept : cap;
         if (overflow) atomicOr(err, 1);
-        if (bad_input) atomicOr(err, 2);
     }
 }
 
@@ -321,9 +426,18 @@ int nms_greedy(ecc_ctx *ctx, const uint32_t *cand, const int32_t *n_cand, int64_
     const int64_t n_slices = (n + slice_events - 1) / slice_events;
     const int half = box_size / 2, cs = 2 * half + 1;
     const int gw = (width + cs - 1) / cs, gh = (height + cs - 1) / cs;
+    // LDS: grid (an even count of words), survivor lists and counts, kept list and count
+    const size_t base = (size_t)(((gw + 2) * (gh + 2) + 1) & ~1) * 4 + (kNmsWaves > 1 ? kNmsWaves * (64 * 8 + 4) : 0);
+    const int kl = (int)std::min<int64_t>(cap, (int64_t)gw * gh);
+    const bool lds_out = kNmsLean && base + (size_t)kl * 4 + 4 <= 65536;  // else the loop stores to out[]
+    const size_t lds = lds_out ? base + (size_t)kl * 4 + 4 : base;
+    const auto fn = lds_out ? &nms_batch_kernel<kNmsWaves, kNmsLean, kNmsLean> : &nms_batch_kernel<kNmsWaves, kNmsLean, false>;
+    if (lds > 65536)
+        if (int rc = ecc::allow_dynamic_lds(ctx, fn, (int)lds, "nms LDS")) return rc;
+    const MagicDiv md = magic_div31((uint32_t)cs);
     ECC_TIMED(ctx, s, "nms_kernel");
-    hipLaunchKernelGGL(nms_greedy_kernel, dim3((unsigned)n_slices), dim3(kGridThreads), (size_t)(gw + 2) * (gh + 2) * 4,
-                       s, cand, n_cand, slice_events, width, height, half, gw, gh, cap, out, out_count, &ctx->dev->nms);
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_slices), dim3(64 * kNmsWaves), lds, s, cand, n_cand, n, slice_events, width,
+                       height, half, gw, gh, cap, lds_out ? kl : 0, md.mul, md.sh, out, out_count, &ctx->dev->nms);
     return ECC_OK;
 }
 }  // namespace ecc

@@ -22,7 +22,7 @@ def short(name: str) -> str:
         return "kmeans_xy16_labels" if re.search(r"<(\d+, )?false[,>]", name) else "kmeans_xy16_kernel"
     if base in ("kmeans_lds_labels_kernel", "kmeans_img_labels_kernel"):
         return "kmeans_xy16_labels"
-    if base in ("nms_grid_kernel", "nms_greedy_kernel"):
+    if base in ("nms_grid_kernel", "nms_greedy_kernel", "nms_batch_kernel"):
         return "nms_kernel"
     if base == "kmeans_step_kernel" and re.search(r"<\d+, true>", name):
         return "kmeans_pixel_pass"
