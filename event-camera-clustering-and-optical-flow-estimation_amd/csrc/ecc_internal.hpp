@@ -90,6 +90,7 @@ struct DevWords {
     int32_t optics_xi[2];      // optics_xi.hip: [0] more pairs than cap, [1] the workspace check fired
     int32_t cluster_stats[2];  // cluster_stats.hip: [0] more runs than cap, [1] invalid order entry or pair
     int32_t optics_xi_tree;    // optics_xi_tree.hip: a segment with more pairs than pair_cap
+    int32_t dbscan_lists[2];   // dbscan_lists.hip: [0] a row or the dups too small, [1] a label or dup out of range
     int64_t box_keys[6];       // radius_grid.hpp: bounding-box keys (3 min, 3 max)
     rgrid::Grid grid;          // radius_grid.hpp: the cloud grid's geometry
 };

@@ -205,6 +205,9 @@ _sigs = {
     "ecc_dbscan_extract": (C.c_int, [P, i64, i64, P, P, P, i64, i32, i32, i32, P, P, P, i64, P, P]),
     "ecc_dbscan_grid": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, i32, i32, P, P, P, i64, P, P]),
     "ecc_dbscan_status": (C.c_int, [P, P]),
+    "ecc_dbscan_lists": (C.c_int, [P, P, P, P, i64, P, i64, i64, P, P, i64, P, P, i64, P]),
+    "ecc_dbscan_lists_status": (C.c_int, [P, P]),
+    "ecc_dbscan_lists_host": (C.c_int, [P, i64, i32, P, i64, P, i64, P, P, i64]),
     "ecc_optics_grid": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, C.c_double, P, P, P, P, P]),
     "ecc_optics_grid_status": (C.c_int, [P, P]),
     "ecc_optics_xi": (C.c_int, [P, P, i64, i64, P, C.c_double, i32, C.c_double, P, i64, P, P]),
@@ -216,6 +219,7 @@ _sigs = {
     "ecc_optics_xi_tree_host": (C.c_int, [P, i64, P, P, P, P]),
     "ecc_cluster_stats_runs": (C.c_int, [P, P, P, P, i64, i64, P, P, i64, P, P]),
     "ecc_cluster_stats_pairs": (C.c_int, [P, P, P, P, i64, P, i64, i64, P, P, P]),
+    "ecc_cluster_stats_lists": (C.c_int, [P, P, P, i64, P, P, i64, P, i64, i64, P, P, P]),
     "ecc_cluster_stats_status": (C.c_int, [P, P]),
     "ecc_cluster_stats_host": (C.c_int, [P, P, i64, P, i64, P]),
     "ecc_device_sync": (C.c_int, []),
@@ -547,6 +551,20 @@ class Context:
     def dbscan_status(self) -> int:
         return lib.ecc_dbscan_status(self.ctx, self.stream)
 
+    def dbscan_lists(self, labels: DeviceArray, n_clusters: DeviceArray, dups: DeviceArray | None, dup_cap: int,
+                     n_dups: DeviceArray, n_segs: int, stride: int, counts_in, members: DeviceArray,
+                     member_stride: int, n_members: DeviceArray, pairs: DeviceArray, pair_cap: int):
+        """The cluster index lists of every segment from dbscan_grid / dbscan_extract / dbscan_cloud's outputs
+        (labels, n_clusters, dups, n_dups): members int32[n_segs * member_stride] (cluster 0's indices
+        ascending, then cluster 1's, ...), n_members int64[n_segs], pairs int32[n_segs * pair_cap * 2]
+        ({begin, end} inclusive positions in the segment's members row)."""
+        check(lib.ecc_dbscan_lists(self.ctx, labels.ptr, n_clusters.ptr, _ptr(dups), dup_cap, n_dups.ptr, n_segs,
+                                   stride, _ptr(counts_in), members.ptr, member_stride, n_members.ptr, pairs.ptr,
+                                   pair_cap, self.stream), "ecc_dbscan_lists")
+
+    def dbscan_lists_status(self) -> int:
+        return lib.ecc_dbscan_lists_status(self.ctx, self.stream)
+
     def optics_grid(self, xy: DeviceArray, n_segs: int, stride: int, counts_in, eps: float, min_pts: int,
                     threshold: float, order: DeviceArray, reach: DeviceArray, cluster: DeviceArray | None = None,
                     n_clusters: DeviceArray | None = None):
@@ -602,6 +620,16 @@ class Context:
         n_clusters): stats CLUSTER_STAT_DTYPE[n_segs * pair_cap], pair k of segment s at s * pair_cap + k."""
         check(lib.ecc_cluster_stats_pairs(self.ctx, xy.ptr, order.ptr, pairs.ptr, pair_cap, n_pairs.ptr, n_segs, stride,
                                           _ptr(counts_in), stats.ptr, self.stream), "ecc_cluster_stats_pairs")
+
+    def cluster_stats_lists(self, xy: DeviceArray, members: DeviceArray, member_stride: int, n_members: DeviceArray,
+                            pairs: DeviceArray, pair_cap: int, n_pairs: DeviceArray, n_segs: int, stride: int,
+                            counts_in, stats: DeviceArray):
+        """The same records for the lists dbscan_lists leaves on the device (members, n_members, pairs and its
+        n_clusters as n_pairs): stats CLUSTER_STAT_DTYPE[n_segs * pair_cap], list c of segment s at
+        s * pair_cap + c, its points walked in list order."""
+        check(lib.ecc_cluster_stats_lists(self.ctx, xy.ptr, members.ptr, member_stride, n_members.ptr, pairs.ptr,
+                                          pair_cap, n_pairs.ptr, n_segs, stride, _ptr(counts_in), stats.ptr,
+                                          self.stream), "ecc_cluster_stats_lists")
 
     def cluster_stats_status(self) -> int:
         return lib.ecc_cluster_stats_status(self.ctx, self.stream)
@@ -866,6 +894,23 @@ def cluster_stats_host(xy, order, pairs):
     rc = lib.ecc_cluster_stats_host(xy.ctypes.data, order.ctypes.data, xy.size, pairs.ctypes.data, len(pairs),
                                     out.ctypes.data)
     return out, rc
+
+
+def dbscan_lists_host(labels, n_clusters, dups, member_cap=None, pair_cap=None):
+    """The cluster index lists of one segment on the host (no GPU): labels int32[n], dups (k, 2) int64
+    (point, cluster) -> (members int32[n_members] or None, pairs int32 (n_clusters, 2) or None, n_members,
+    status); members and pairs are None when they did not fit member_cap / pair_cap (ERR_CAPACITY)."""
+    labels = np.ascontiguousarray(labels, np.int32)
+    dups = np.ascontiguousarray(dups, np.int64).reshape(-1, 2)
+    member_cap = len(labels) + len(dups) if member_cap is None else member_cap
+    pair_cap = max(int(n_clusters), 0) if pair_cap is None else pair_cap
+    members, pairs = np.zeros(max(member_cap, 1), np.int32), np.zeros((max(pair_cap, 1), 2), np.int32)
+    n_members = C.c_int64(0)
+    rc = lib.ecc_dbscan_lists_host(labels.ctypes.data, len(labels), int(n_clusters), dups.ctypes.data, len(dups),
+                                   members.ctypes.data, member_cap, C.addressof(n_members), pairs.ctypes.data, pair_cap)
+    if n_members.value > member_cap or max(int(n_clusters), 0) > pair_cap:
+        return None, None, n_members.value, rc
+    return members[:n_members.value], pairs[:max(int(n_clusters), 0)], n_members.value, rc
 
 
 def pack_xy(x, y) -> np.ndarray:

@@ -671,7 +671,8 @@ std::vector<std::vector<std::size_t>> get_cluster_indices(const std::vector<reac
 void DBSCANSimpleCluster::extract(std::vector<PointIndices> &cluster_indices) {  // DBSCAN_simple.h:27-90
     // The reference's own input (float x, y, z; any size): radiusSearch (:118-142) and the
     // seed-queue expansion (union-find closed form) both run on the GPU over one global cell grid
-    // (ecc_dbscan_cloud_f32); the host only turns labels + duplicate memberships into PointIndices.
+    // (ecc_dbscan_cloud_f32), and so does the grouping into sorted lists (ecc_dbscan_lists); the
+    // host only cuts the downloaded members row at the {begin, end} pairs.
     cluster_indices.clear();
     const int64_t n = (int64_t)cloud_.size();
     if (n == 0) return;
@@ -698,20 +699,33 @@ void DBSCANSimpleCluster::extract(std::vector<PointIndices> &cluster_indices) { 
         break;
     }
     int32_t nc = 0;
-    std::vector<int32_t> lab(n);
     d_nc.download(&nc, 4, s);
-    d_lab.download(lab.data(), n * 4, s);
-    std::vector<int64_t> dups((size_t)nd * 2);
-    if (nd) d_dups.download(dups.data(), (size_t)nd * 16, s);
     ctx_.sync();
-    std::vector<std::vector<int>> members((size_t)nc);
-    for (int64_t i = 0; i < n; ++i)
-        if (lab[i] >= 0) members[lab[i]].push_back((int)i);
-    for (int64_t k = 0; k < nd; ++k) members[dups[2 * k + 1]].push_back((int)dups[2 * k]);
-    for (auto &m : members) {
-        std::sort(m.begin(), m.end());  // :82
-        cluster_indices.push_back(PointIndices{m});
-    }
+    // every labelled point once plus the further memberships: at most n + nd entries
+    const int64_t member_cap = n + nd, pair_cap = std::max<int32_t>(nc, 1);
+    if (member_cap > INT32_MAX) throw Error(ECC_ERR_CAPACITY, "ecc_dbscan_lists");
+    DeviceBuffer d_mem((size_t)member_cap * 4), d_nm(8), d_pairs((size_t)pair_cap * 8);
+    // one segment: a stride above the window limit selects the any-size path for clouds of every size
+    const int64_t stride = std::max<int64_t>(n, 8193);
+    DeviceBuffer d_cnt(4);
+    const int32_t count = (int32_t)n;
+    d_cnt.upload(&count, 4, s);
+    check(ecc_dbscan_lists(ctx_.get(), d_lab.as<int32_t>(), d_nc.as<int32_t>(), d_dups.as<int64_t>(), dup_cap,
+                           d_nd.as<int64_t>(), 1, stride, d_cnt.as<int32_t>(), d_mem.as<int32_t>(), member_cap,
+                           d_nm.as<int64_t>(), d_pairs.as<int32_t>(), pair_cap, s),
+          "ecc_dbscan_lists");
+    check(ecc_dbscan_lists_status(ctx_.get(), s), "ecc_dbscan_lists");
+    int64_t nm = 0;
+    d_nm.download(&nm, 8, s);
+    std::vector<int32_t> pairs((size_t)nc * 2);
+    if (nc) d_pairs.download(pairs.data(), (size_t)nc * 8, s);
+    ctx_.sync();
+    std::vector<int32_t> members((size_t)nm);
+    if (nm) d_mem.download(members.data(), (size_t)nm * 4, s);
+    ctx_.sync();
+    for (int32_t c = 0; c < nc; ++c)
+        cluster_indices.push_back(
+            PointIndices{std::vector<int>(members.begin() + pairs[2 * c], members.begin() + pairs[2 * c + 1] + 1)});
 }
 
 }  // namespace ecc

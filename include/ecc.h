@@ -603,6 +603,60 @@ int ecc_dbscan_grid(ecc_ctx *ctx, const uint32_t *xy, int64_t n_segs, int64_t se
                     int64_t dup_cap, int64_t *n_dups, ecc_stream_t stream);
 int ecc_dbscan_status(ecc_ctx *ctx, ecc_stream_t stream);
 
+/* ecc_dbscan_lists: the cluster index lists of every segment on the device, from what
+ * ecc_dbscan_grid / ecc_dbscan_extract / ecc_dbscan_cloud_* leave there.
+ * Reference: what DBSCANSimpleCluster::extract returns, std::vector<pcl::PointIndices>
+ *   (PCC/DBSCAN_simple.h:27-90): clusters in output order, each cluster's indices sorted
+ *   ascending (:82), a border point in every cluster that reached it; consumed cluster by
+ *   cluster at PCC/pcl_cluster.cpp:131-142.
+ * Inputs (DEVICE), exactly as the three DBSCAN entries leave them: labels[s*seg_stride + j] a
+ *   cluster index or -1; n_clusters[s]; dups (flattened point, cluster index) pairs of which
+ *   min(*n_dups, dup_cap) are read; seg_counts NULL = full segments.
+ * Outputs (DEVICE) for segment s with C = n_clusters[s]:
+ *   members[s*member_stride + i] = the segment-local indices of cluster 0, then cluster 1, ...; a
+ *     cluster's members are every j < seg_counts[s] with labels == c and every dup pair (p, c) of
+ *     this segment, ascending; a membership given twice is listed twice; points with label -1 and
+ *     no dup are not listed;
+ *   pairs[(s*pair_cap + c)*2 .. +1] = {begin, end}, inclusive positions in the segment's members
+ *     row (the interval form of ecc_optics_xi); an empty cluster (fabricated input) is
+ *     {begin, begin - 1};
+ *   n_members[s] = the number of memberships, always written.
+ *   The output bytes do not depend on the order of dups.
+ * Capacity is all or nothing per segment: with n_members[s] > member_stride or C > pair_cap only
+ *   n_members[s] is written for that segment, other segments are unaffected, and the status is
+ *   ECC_ERR_CAPACITY — as it is when *n_dups > dup_cap (the DBSCAN call dropped memberships).
+ *   Entries past a segment's memberships, past its C pairs, and the rows' remainders are untouched.
+ * Never used as an index, ignored, and reported as ECC_ERR_INVALID: a label outside [-1, C); a dup
+ *   whose point lies outside [0, n_segs*seg_stride) or at a slot >= seg_counts[s], or whose cluster
+ *   lies outside [0, C); a negative n_clusters[s] (counts as 0).
+ * seg_stride <= 8192: any number of segments, one workgroup each; up to 16384 memberships (and
+ *   2^18 clusters) of a segment are sorted in LDS; a segment with more is placed through its own
+ *   output rows at a cost quadratic in its memberships.  seg_stride > 8192: one segment of any
+ *   size, through a device radix sort.  The contract is the same.
+ * Uses the context workspace (grown on the first call: not inside a stream capture).
+ * ECC_ERR_INVALID (before any launch): NULL ctx; NULL labels / n_clusters / n_dups / members /
+ * n_members / pairs with n_segs > 0; NULL dups with dup_cap > 0; n_segs, dup_cap or pair_cap < 0;
+ * seg_stride outside [1, INT32_MAX]; member_stride outside [0, INT32_MAX]; seg_stride > 8192 with
+ * n_segs > 1.  n_segs == 0: ECC_OK after the same checks.
+ * ecc_dbscan_lists_status (of the last call; synchronises `stream`): ECC_ERR_INVALID, else
+ * ECC_ERR_CAPACITY, as above; ECC_ERR_INVALID for NULL ctx. */
+int ecc_dbscan_lists(ecc_ctx *ctx, const int32_t *labels, const int32_t *n_clusters, const int64_t *dups,
+                     int64_t dup_cap, const int64_t *n_dups, int64_t n_segs, int64_t seg_stride,
+                     const int32_t *seg_counts, int32_t *members, int64_t member_stride, int64_t *n_members,
+                     int32_t *pairs, int64_t pair_cap, ecc_stream_t stream);
+int ecc_dbscan_lists_status(ecc_ctx *ctx, ecc_stream_t stream);
+/* ecc_dbscan_lists_host (DBSCAN_simple.h:27-90, :82): the same product for ONE segment of n slots in
+ * HOST memory, on the host (no GPU, no context): push_back per label and per dup, std::sort per
+ * cluster.  dups: n_dups (point, cluster) pairs.  members: HOST int32[member_cap]; pairs: HOST
+ * int32[pair_cap * 2]; *n_members is always written.  ECC_ERR_INVALID (nothing written): n outside
+ * [0, INT32_MAX], n_dups, member_cap or pair_cap < 0, NULL n_members, NULL labels with n > 0, NULL
+ * dups with n_dups > 0; or, after the lists are written, an ignored label, dup or negative
+ * n_clusters as above.  ECC_ERR_CAPACITY (only *n_members written): more memberships than member_cap
+ * or more clusters than pair_cap. */
+int ecc_dbscan_lists_host(const int32_t *labels, int64_t n, int32_t n_clusters, const int64_t *dups,
+                          int64_t n_dups, int32_t *members, int64_t member_cap, int64_t *n_members,
+                          int32_t *pairs, int64_t pair_cap);
+
 /* ecc_optics_grid: the OPTICS ordering of every segment, and optionally its threshold clusters,
  * in one launch (one workgroup per segment; the same segment conventions as ecc_dbscan_grid,
  * seg_stride <= 8192, seg_counts NULL = full segments, duplicates allowed).
@@ -740,6 +794,22 @@ int ecc_cluster_stats_runs(ecc_ctx *ctx, const uint32_t *xy, const int32_t *orde
                            ecc_cluster_stat *stats, int64_t cap, int32_t *n_stats, ecc_stream_t stream);
 int ecc_cluster_stats_pairs(ecc_ctx *ctx, const uint32_t *xy, const int32_t *order, const int32_t *pairs,
                             int64_t pair_cap, const int32_t *n_pairs, int64_t n_segs, int64_t seg_stride,
+                            const int32_t *seg_counts, ecc_cluster_stat *stats, ecc_stream_t stream);
+/* ecc_cluster_stats_lists: the same record for every list ecc_dbscan_lists leaves on the device
+ * (the reference computes these statistics only for OPTICS clusters; their use on DBSCAN lists is
+ * this project's extension, the same fp64 chain :472-527 walked in list order).  members,
+ * member_stride, n_members take the place of `order`: interval k < min(n_pairs[s], pair_cap) of
+ * segment s is positions begin..end of the segment's members row, its points xy[s*seg_stride +
+ * members[..]].  A row may be longer than the segment (a membership given twice), so a pair is
+ * bounded by min(n_members[s], member_stride), not by seg_counts[s]; a members value must lie in
+ * [0, seg_counts[s]).  A pair with begin > end (an empty cluster), begin < 0, end past that bound, or
+ * holding such a members value gives {begin, 0, 0, 0, 0, 0} and ECC_ERR_INVALID from
+ * ecc_cluster_stats_status.  n_pairs is ecc_dbscan_lists' n_clusters.  ECC_ERR_INVALID (before any
+ * launch): as ecc_cluster_stats_pairs, with members / n_members for order, and member_stride outside
+ * [0, INT32_MAX]. */
+int ecc_cluster_stats_lists(ecc_ctx *ctx, const uint32_t *xy, const int32_t *members, int64_t member_stride,
+                            const int64_t *n_members, const int32_t *pairs, int64_t pair_cap,
+                            const int32_t *n_pairs, int64_t n_segs, int64_t seg_stride,
                             const int32_t *seg_counts, ecc_cluster_stat *stats, ecc_stream_t stream);
 int ecc_cluster_stats_status(ecc_ctx *ctx, ecc_stream_t stream);
 /* ecc_cluster_stats_host (cluster_event_data.cpp:472-527): the same loop for the n_pairs intervals

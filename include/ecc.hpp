@@ -23,6 +23,9 @@
 //   DBSCANSimpleCluster / DBSCANPrecompCluster::{setInputCloud, setClusterTolerance,
 //     setCorePointMinPts, setMin/MaxClusterSize, extract}
 //                                    PCC/DBSCAN_simple.h:14-143, DBSCAN_precomp.h  ecc::DBSCANSimpleCluster ...
+//   the same extract per downsample window, and the statistics of its lists
+//                                    PCC/DBSCAN_simple.h:27-90      ecc::dbscan_extract_windows,
+//                                                                  ecc::dbscan_statistics_windows
 //   process_coordinates + host slice path  SMP/…opencl_store.cpp:250-417  ecc::HashDownsampler
 //   assign_to_centers + k-means host loop  KM/assign_to_centers2.c:184-548 ecc::KMeans
 //   the same loop per slice + centroid - centroid_prev[id]
@@ -634,6 +637,22 @@ class DBSCANPrecompCluster : public DBSCANSimpleCluster {
     double searchTolerance() const override { return precomp_eps_; }
     double precomp_eps_{0.0};
 };
+
+// DBSCANSimpleCluster::extract (DBSCAN_simple.h:27-90) for many windows of packed u16 xy points
+// already on the DEVICE, laid out as ecc_downsample_hash leaves them (seg_stride <= 8192,
+// device_seg_counts null = full segments): ecc_dbscan_grid, then ecc_dbscan_lists, one launch each
+// for all windows; the host only cuts the downloaded rows.  One vector of clusters per window, in
+// output order, indices local to the window and ascending (:82).  Synchronises the context's stream.
+std::vector<std::vector<PointIndices>> dbscan_extract_windows(Context &ctx, const uint32_t *device_xy, int64_t n_segs,
+                                                              int64_t seg_stride, const int32_t *device_seg_counts,
+                                                              double eps, int min_pts, int min_cluster_size = 1,
+                                                              int max_cluster_size = 1 << 30);
+// Size, centroid and per-axis variance of each of those clusters (ecc_cluster_stats_lists: the
+// record of optics::cluster_statistics over the list's points in list order; the reference computes
+// it for OPTICS clusters only).  begin is the cluster's first position in the window's members row.
+std::vector<std::vector<optics::cluster_stat<2>>> dbscan_statistics_windows(
+    Context &ctx, const uint32_t *device_xy, int64_t n_segs, int64_t seg_stride, const int32_t *device_seg_counts,
+    double eps, int min_pts, int min_cluster_size = 1, int max_cluster_size = 1 << 30);
 
 // Neighbour lists of 2-D integer points (x,y of the cloud) on the GPU: CSR, ascending indices
 // (DBSCAN_precomp.h's adjacency row order); any number of points and any min_pts.
