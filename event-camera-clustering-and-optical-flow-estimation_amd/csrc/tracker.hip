@@ -17,6 +17,7 @@
 // velocities and directions are bit-identical to oracle/oracle.cpp (std::pow(0.8f, i-1) is a
 // host-side table, :254).
 #include "ecc_internal.hpp"
+#include "tracker_paths.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -28,6 +29,8 @@
 #endif
 
 namespace {
+
+using namespace trk_paths;  // the switch points (kFT, kBrute, grid_ok, ...)
 
 #if ECC_TRACKER_PROFILE
 // wall-clock ticks per phase (thread 0, after the phase's barrier) + matching rounds
@@ -42,7 +45,6 @@ __device__ unsigned long long g_trk_prof[16];
 #define TRK_MARK(k) do { } while (0)
 #endif
 
-constexpr int kNT = 512;                         // one workgroup of 8 waves (2 per SIMD)
 constexpr int kH = ECC_TRACK_HIST_MAX;
 constexpr int kMaxTrk = ECC_TRACKER_MAX_TRACKS;  // active tracks of a slice held in LDS
 constexpr int kMaxDet = ECC_TRACKER_MAX_DETECTIONS;
@@ -182,19 +184,12 @@ __device__ __forceinline__ F2 predict(const DevTrack &t, const TrackerParams &p)
 static_assert(kMaxTrk == kMaxDet, "ck_x/ck_y overlay the prediction arrays");
 static_assert(kMaxTrk <= 4096, "track index packs into 12 bits of the matching tag");
 static_assert(64 * 16 <= 2 * kMaxTrk, "member staging fits the st array");
+static_assert(kTailTracks <= 64 && kFTailTracks <= 64 && kGroupWave <= 64, "one lane of a wave each");
 
 // Detection grid for the matching scans: cells of kCell >= 2 * (max_distance + 1) + 2 pixels
 // hashed into kBuckets buckets, so every detection a prediction can reach lies in at most 3 x 3
 // cells.  Collisions only add candidates (the argmin is taken over (dist, index) explicitly).
-constexpr int kBuckets = 512;
-constexpr int kBrute = 384;
-constexpr int kLaneList = 4;  // in-range detections a matching lane keeps in registers
-constexpr int kTailCap = 1024; // candidate entries of the one-wave matching tail  // up to this many detections a scan walks all of them (uniform, no grid)  // per-track candidate list held in registers during the matching rounds
-__device__ __forceinline__ int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-__device__ __forceinline__ int cell_bucket(int cx, int cy) {
-    return (int)(((uint32_t)cx * 0x9E3779B1u ^ (uint32_t)cy * 0x85EBCA77u) >> (32 - 9));
-}
-static_assert(kBuckets == 1 << 9, "bucket hash takes the top 9 bits");
+// (kBuckets, kBrute, kLaneList, kTailCap, floor_div and cell_bucket: tracker_paths.hpp)
 
 // Exclusive scan of v[0..kBuckets) in place (one entry per thread); v[kBuckets] = total.
 __device__ __forceinline__ void block_scan_buckets(int *v, int *ws) {
@@ -297,7 +292,7 @@ __device__ __forceinline__ void group_slice(const GroupLds L, int G, bool last, 
 #define GRP_MARK(k) do { } while (0)
 #endif
     int n_groups = 0, n_glabels = 0;
-    if (G <= 64) {
+    if (G <= kGroupWave) {
         // one candidate per lane, in registers: seed search and membership are ballots
         const bool valid = lane < G;
         const int mx = valid ? L.ck_x[lane] : 0, my = valid ? L.ck_y[lane] : 0;
@@ -528,10 +523,10 @@ tracker_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__restr
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // |dx| or |dy| above max_distance + 1 cannot give dist < max_distance (for sane radii)
-    const float reach = __fadd_rn(p.max_distance, 1.0f);
+    const float reach = grid_reach(p.max_distance);
     // grid matching for sane radii; otherwise every scan walks all detections
-    const bool grid_ok = p.max_distance >= 0.0f && p.max_distance < 1.0e5f;
-    const int cell = grid_ok ? (int)ceilf(reach) + 1 : 1;
+    const bool grid_ok = trk_paths::grid_ok(p.max_distance);
+    const int cell = grid_cell(p.max_distance);
     const int s0 = ctr->resume;  // slices before it were processed by tracker_fast_kernel
     if (s0 >= n_slices) return;
     int T = ctr->n_tracks, next_label = ctr->next_label, cur = ctr->cur, err = ctr->err;
@@ -600,10 +595,8 @@ tracker_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__restr
         // dist < max_distance from the prediction pp.
         auto visit_grid = [&](const F2 pp, bool check_claims, auto &&f) {
             // the cells of the integer box [pp - reach, pp + reach]: at most 3 x 3
-            const int cx0 = floor_div((int)floorf(__fsub_rn(pp.x, reach)), cell);
-            const int cx1 = floor_div((int)ceilf(__fadd_rn(pp.x, reach)), cell);
-            const int cy0 = floor_div((int)floorf(__fsub_rn(pp.y, reach)), cell);
-            const int cy1 = floor_div((int)ceilf(__fadd_rn(pp.y, reach)), cell);
+            const int cx0 = grid_cell_lo(pp.x, reach, cell), cx1 = grid_cell_hi(pp.x, reach, cell);
+            const int cy0 = grid_cell_lo(pp.y, reach, cell), cy1 = grid_cell_hi(pp.y, reach, cell);
             int seen[9], ns = 0;
             for (int cy = cy0; cy <= cy1; ++cy)
                 for (int cx = cx0; cx <= cx1; ++cx) {
@@ -626,13 +619,12 @@ tracker_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__restr
         // L lanes per track (a power of two, T * L <= kNT): lane jl of a track's group scans
         // detections jl, jl + L, ...; the group combines its (dist, index) minima with shuffles.
         int L = 1;
-        if (!use_grid)
-            while (L < 64 && T * L * 2 <= kNT) L <<= 1;
+        ECC_TRK_GENERAL_LANES(L, T, use_grid);
         const int jl = tid & (L - 1);
         // Each lane's in-range detections of the first round stay in registers (the lane owns one
         // track when T * L <= kNT), so later rounds only re-check claims; a lane with more than
         // kLaneList of them rescans its share instead.
-        const bool lists_ok = T <= kNT / L;
+        const bool lists_ok = trk_paths::lists_ok(T, L);
         float l_d[kLaneList];
         int l_i[kLaneList];
         int l_n = 0;
@@ -727,7 +719,7 @@ tracker_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__restr
                 }
                 off = __shfl(off, lane & ~(L - 1));
                 __syncthreads();
-                const bool tail_ok = n_unres <= 64 && s_tail[1] == 0 && s_tail[0] <= kTailCap;
+                const bool tail_ok = n_unres <= kTailTracks && s_tail[1] == 0 && s_tail[0] <= kTailCap;
                 if (tail_ok) {
                     if (head) {
                         t_trk[u] = (int16_t)i;
@@ -948,10 +940,8 @@ __device__ __forceinline__ int qperm(int v) { return __builtin_amdgcn_mov_dpp(v,
 template <int kCtrl>
 __device__ __forceinline__ float qperm_f(float v) { return __int_as_float(qperm<kCtrl>(__float_as_int(v))); }
 
-constexpr int kFT = 256;    // the largest T + C of a slice handled here (LDS arrays)
-constexpr int kFThreads = 512;  // 8 waves: the round-0 scan runs 2-4 lanes per track
+// (kFT, kFThreads, kFList and the round-0 scan's lane and chunk rules: tracker_paths.hpp)
 constexpr int kFW = kFThreads / 64;
-constexpr int kFList = 8;   // in-range detections a track keeps in registers (more: it rescans)
 constexpr int kFTagTop = (1 << 23) - 1;  // round tags: ((kFTagTop - round) << 8) | track
 static_assert(kFT <= 256, "track index packs into 8 bits of the matching tag");
 
@@ -1152,7 +1142,7 @@ tracker_fast_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__
         // order, is the minimum of (dist, index) over its lanes; its in-range detections are
         // merged into one list (order irrelevant) for the later rounds.
         {
-            const int lsh = T <= 128 ? 2 : 1;  // uniform: L = 1 << lsh, T * L <= kFThreads
+            const int lsh = fast_lane_shift(T);  // uniform: L = 1 << lsh, T * L <= kFThreads
             const int L = 1 << lsh;
             const int ti = tid >> lsh, tj = tid & (L - 1);
             const bool act = ti < T && f_st[ti] == -3;
@@ -1206,10 +1196,10 @@ tracker_fast_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__
                 }
             };
             if (act) {
-                if (C <= 16 * L)
-                    scan(std::integral_constant<int, 16>{});
+                if (fast_chunk_narrow(C, L))
+                    scan(std::integral_constant<int, kFChunkNarrow>{});
                 else
-                    scan(std::integral_constant<int, 32>{});
+                    scan(std::integral_constant<int, kFChunkWide>{});
             }
             // the track's lanes: minimum, list sizes -> merged list offsets
             // (quad DPP permutes: L = 2 or 4 lanes of a track lie in one quad; the lane shuffles
@@ -1277,7 +1267,7 @@ tracker_fast_kernel(DevTrack *buf0, DevTrack *buf1, int max_tracks, DevGroup *__
                 n_unres += f_ws[w];
                 n_ovf += f_ws[kFW + w];
             }
-            if (n_unres > 0 && n_unres <= 64 && n_ovf == 0) {
+            if (n_unres > 0 && n_unres <= kFTailTracks && n_ovf == 0) {
                 if (unres) f_tail[u] = (int16_t)tid;
                 __syncthreads();
                 if (wave == 0) {

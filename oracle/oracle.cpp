@@ -597,6 +597,7 @@ ORC_API int orc_tracker_update(void *tr, const ecc_corner *cs, int n) {
     static_cast<OrcTracker *>(tr)->update(cs, n);
     return 0;
 }
+ORC_API int orc_tracker_next_label(void *tr) { return static_cast<OrcTracker *>(tr)->next_label; }
 ORC_API int orc_tracker_get_tracks(void *trp, ecc_track *out, int cap) {
     OrcTracker *tr = static_cast<OrcTracker *>(trp);
     const int n = (int)tr->tracks.size();

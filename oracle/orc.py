@@ -41,6 +41,7 @@ _sigs = {
     "orc_tracker_create": (P, [P]),
     "orc_tracker_destroy": (None, [P]),
     "orc_tracker_update": (C.c_int, [P, P, i32]),
+    "orc_tracker_next_label": (C.c_int, [P]),
     "orc_tracker_get_tracks": (C.c_int, [P, P, i32]),
     "orc_tracker_get_groups": (C.c_int, [P, P, i32, P, i32]),
     "orc_eps_neighbours": (C.c_int, [P, i64, i64, P, f64, i32, P, P, P, P, i64]),
@@ -171,6 +172,9 @@ class OracleTracker:
     def update(self, corners: np.ndarray):
         corners = np.ascontiguousarray(corners, CORNER_DTYPE)
         lib.orc_tracker_update(self.h, _p(corners), len(corners))
+
+    def next_label(self) -> int:
+        return lib.orc_tracker_next_label(self.h)
 
     def tracks(self, track_type, cap=65536):
         buf = (track_type * cap)()

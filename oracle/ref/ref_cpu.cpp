@@ -198,6 +198,11 @@ void put_tracker(Words &o, const std::vector<TrackedCorner> &tr, const std::map<
     }
 }
 
+// The command-line interface's number, printed by `ref_cpu api` (tests/ref_cpu_cases.py:REF_CPU_API):
+// a binary left in oracle/_ref/ by another revision of this file answers another number or none.
+// 2: track takes a configuration.
+constexpr int kRefCpuApi = 2;
+
 CornerTracker make_tracker() {  // as main() constructs it (:805-813)
     return CornerTracker(30.0f, 30, 10, 5, 0.8f, 0.3f, 100.0f);
 }
@@ -265,11 +270,27 @@ int cmd_nms(int argc, char **argv) {
     return 0;
 }
 
-// track IN_LISTS(x, y, label) OUT_DUMP
+// The constructor's seven arguments as one word each, comma-separated hex: max_distance (float
+// bits), max_frames, history_size, frames_to_skip (int bits), damping, smoothing, group_radius
+// (float bits).  Bit patterns, so that NaN and an exact radius arrive as they were meant.
+CornerTracker make_tracker(const char *cfg) {
+    uint32_t w[7];
+    const char *q = cfg;
+    for (int k = 0; k < 7; ++k) {
+        char *end = nullptr;
+        w[k] = (uint32_t)std::strtoul(q, &end, 16);
+        if (end == q || *end != (k < 6 ? ',' : '\0')) die("track: the configuration is seven hex words");
+        q = end + 1;
+    }
+    const auto f = [&](int k) { float v; std::memcpy(&v, &w[k], 4); return v; };
+    return CornerTracker(f(0), (int)w[1], (int)w[2], (int)w[3], f(4), f(5), f(6));
+}
+
+// track IN_LISTS(x, y, label) OUT_DUMP [CFG]
 int cmd_track(int argc, char **argv) {
-    if (argc != 4) die("track: wrong argument count");
+    if (argc != 4 && argc != 5) die("track: wrong argument count");
     const auto in = get_lists(read_file<int32_t>(argv[2]), 3);
-    CornerTracker tracker = make_tracker();
+    CornerTracker tracker = argc == 5 ? make_tracker(argv[4]) : make_tracker();
     Words o;
     o.i((int)in.size());
     for (const auto &c : in) {
@@ -344,8 +365,9 @@ int cmd_aec(int argc, char **argv) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    if (argc < 2) die("usage: ref_cpu arc|chain|nms|track|dbscan|aec …");
+    if (argc < 2) die("usage: ref_cpu api|arc|chain|nms|track|dbscan|aec …");
     const std::string c = argv[1];
+    if (c == "api") { std::printf("%d\n", kRefCpuApi); return 0; }
     if (c == "arc") return cmd_arc(argc, argv, false);
     if (c == "chain") return cmd_arc(argc, argv, true);
     if (c == "nms") return cmd_nms(argc, argv);

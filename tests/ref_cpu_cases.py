@@ -8,6 +8,9 @@ was absent at build time) they come from tests/golden/ref_cpu/<case>.npz: what t
 for the same inputs, stored by running the CPU module with ECC_RECORD_REF_GOLDEN=1 where it is
 built.  Every fixture carries a SHA-256 of the generated input it answers, checked on load, so a
 changed generator cannot be compared with stale answers.  With neither present a test fails.
+A binary that another revision of oracle/ref/ref_cpu.cpp left in oracle/_ref/ (it is kept out of
+git, and without the reference tree nothing rebuilds it) counts as not built: `ref_cpu api` must
+answer REF_CPU_API.  A binary that answers no interface number at all fails the test.
 
 The final time surface (7 MB) is kept in a fixture as its SHA-256 only; `same_surface` compares
 whichever is at hand.
@@ -37,6 +40,36 @@ def sha(*parts):
     return h.hexdigest()
 
 
+REF_CPU_API = 2  # oracle/ref/ref_cpu.cpp:kRefCpuApi
+_USABLE = {}
+
+
+def ref_cpu_usable():
+    """oracle/_ref/ref_cpu is there and was built from this tree's oracle/ref/ref_cpu.cpp: `ref_cpu api`
+    answers REF_CPU_API.  oracle/_ref/ is kept out of git, so a binary of another revision can lie
+    there where the reference tree is absent and nothing rebuilds it.  Only such a binary counts as
+    not built (the recorded answers stand in, with a warning): one that answers another number, or
+    interface 1, which has no `api` and declines it as an unknown subcommand with status 2.  A binary
+    that answers anything else - nothing, no integer, a crash - fails the test."""
+    if "ref_cpu" not in _USABLE:
+        ok = False
+        if REF_CPU.exists():
+            r = subprocess.run([str(REF_CPU), "api"], capture_output=True, text=True, timeout=60)
+            if r.returncode == 2 and r.stdout == "" and "unknown subcommand" in r.stderr:
+                api = 1
+            else:
+                assert r.returncode == 0 and r.stdout.strip().isdigit(), \
+                    f"{REF_CPU} api: status {r.returncode}, {r.stdout[-200:]!r}, {r.stderr[-200:]!r}"
+                api = int(r.stdout)
+            ok = api == REF_CPU_API
+            if not ok:
+                import warnings
+                warnings.warn(f"{REF_CPU} has interface {api}, oracle/ref/ref_cpu.cpp {REF_CPU_API}: "
+                              "the recorded answers of tests/golden/ref_cpu are used instead")
+        _USABLE["ref_cpu"] = ok
+    return _USABLE["ref_cpu"]
+
+
 def _ref(case, tmp_path, sub, inputs, args, outputs, digest_only=(), exe=None, store=None, restore=None):
     """Runs `ref_cpu sub` (or loads the stored run).  inputs: {file name: array}; args: the argument
     list with input/output file NAMES in place of paths; outputs: {file name: dtype}.  Returns
@@ -48,7 +81,7 @@ def _ref(case, tmp_path, sub, inputs, args, outputs, digest_only=(), exe=None, s
     key = sha(sub, [a for a in args if a not in inputs and a not in outputs],
               *[inputs[k] for k in sorted(inputs)])
     stored = GOLDEN / f"{case}.npz"
-    if exe.exists():
+    if ref_cpu_usable() if exe == REF_CPU else exe.exists():
         d = tmp_path / f"ref_{case}"
         d.mkdir(exist_ok=True)
         for name, a in inputs.items():
@@ -183,8 +216,19 @@ def ref_nms(case, tmp_path, lists):
     return unpack_lists(r["out.i32"], 3)
 
 
-def ref_track(case, tmp_path, lists3):
-    r = _ref(case, tmp_path, "track", {"in.i32": pack_lists(lists3, 3)}, ["in.i32", "out.i32"], {"out.i32": np.int32})
+def cfg_words(cfg):
+    """A tracker configuration (max_distance, max_frames, history_size, frames_to_skip, damping,
+    smoothing, group_radius) as ref_cpu's argument: seven hex words, the floats as bit patterns."""
+    md, mf, hs, fts, da, sm, gr = cfg
+    return ",".join("%08x" % w for w in (fbits(md), mf & 0xffffffff, hs & 0xffffffff, fts & 0xffffffff,
+                                        fbits(da), fbits(sm), fbits(gr)))
+
+
+def ref_track(case, tmp_path, lists3, cfg=None):
+    """cfg=None: the reference's own CornerTracker(30, 30, 10, 5, 0.8, 0.3, 100); else the seven
+    constructor arguments, which enter the fixture's input hash."""
+    args = ["in.i32", "out.i32"] + ([cfg_words(cfg)] if cfg is not None else [])
+    r = _ref(case, tmp_path, "track", {"in.i32": pack_lists(lists3, 3)}, args, {"out.i32": np.int32})
     return unpack_tracker(r["out.i32"])
 
 

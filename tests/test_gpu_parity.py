@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import parity
+
 pytestmark = pytest.mark.gpu
 
 W_SMALL, H_SMALL = 346, 260
@@ -829,12 +831,7 @@ def test_nms_status_capacity_and_outside(ecc, gpu):
 
 
 # ------------------------------------------------------------------------------ tracker
-def _track_key(tr):
-    return (tr.x, tr.y, tr.label, tr.frame_count, tr.is_matched, tr.frames_since_last_detection,
-            tr.hist_len, tuple(tr.hist_x[:tr.hist_len]), tuple(tr.hist_y[:tr.hist_len]),
-            np.float32(tr.vx).view(np.uint32), np.float32(tr.vy).view(np.uint32),
-            np.float32(tr.dir_cur_x).view(np.uint32), np.float32(tr.dir_cur_y).view(np.uint32),
-            tr.group_id)
+_track_key = parity.track_key  # every field, fp32 as bit patterns (the direction targets too)
 
 
 def test_tracker_matches_oracle(ecc, orc, gpu):
