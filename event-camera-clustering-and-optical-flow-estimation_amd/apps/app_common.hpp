@@ -1,5 +1,5 @@
 // Shared helpers of the host programs: event input as argv[1], the way the reference mains take
-// Camera::from_file(argv[1]) — a Prophesee RAW recording (EVT 2.0 / 3.0, GPU-decoded), a CSV
+// Camera::from_file(argv[1]) — a Prophesee RAW recording (EVT 2.0 / 2.1 / 3.0, GPU-decoded), a CSV
 // "x,y,t,p" file, or --synthetic N for a seeded stream.
 #pragma once
 #include <cstdio>

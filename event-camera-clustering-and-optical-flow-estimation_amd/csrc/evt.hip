@@ -1,11 +1,11 @@
-// Event ingest on the GPU: EVT 2.0 / EVT 3.0 RAW decoders and the n-µs reslicer (SURVEY.md
-// §8f rank 1).
+// Event ingest on the GPU: EVT 2.0 / EVT 2.1 / EVT 3.0 RAW decoders and the n-µs reslicer
+// (SURVEY.md §8f rank 1).
 //
 // Reference: the host programs decode through Metavision::Camera::from_file(argv[1])
 // (FCT/…group_track.cpp:756-760) and slice with EventBufferReslicerAlgorithm
 // (make_n_events :772-774, make_n_us DSA/…opencl_store.cpp:351) on one CPU decode thread.
 // Metavision/OpenEB is not vendored; the word formats restated here are the published
-// EVT 2.0 / EVT 3.0 specifications (include/ecc.h §8).
+// EVT 2.0 / EVT 2.1 / EVT 3.0 specifications (include/ecc.h §8).
 //
 // MI355X design.  Both formats are state machines over a word stream (EVT 2.0: the last
 // TIME_HIGH; EVT 3.0: the last y, TIME_LOW, TIME_HIGH + loop count, vector base x and
@@ -22,6 +22,10 @@
 //      into an LDS window of decoded events and writes the window out coalesced.
 // Algorithmic bytes: words read twice (2 x 2 B or 2 x 4 B per word) + 13 B per event out
 // (xy u32, t i64, p u8); EVT 3.0 adds the lane prefixes (16 B per 32 words, written + read).
+//
+// EVT 2.1 (64-bit words, 32 pixels per CD word) shares phase 2 and has kernels of its own for
+// phases 1 and 3: a lane's 64 B of words hold 0 to 256 events, so evt21_decode_kernel hands
+// each lane output events, not its own words (see there).
 #include "ecc_internal.hpp"
 
 namespace {
@@ -196,6 +200,28 @@ struct Evt2 {
     }
 };
 
+// ---- EVT 2.1 -------------------------------------------------------------------------------
+// 64-bit words, type = w >> 60:
+//   0x0 EVT_NEG / 0x1 EVT_POS: ts6 = w >> 54 & 0x3F, x = w >> 43 & 0x7FF, y = w >> 32 & 0x7FF,
+//       valid = w & 0xFFFFFFFF: one event per set bit b, x + b, in ascending b
+//   0x8 EVT_TIME_HIGH: th = w >> 32 & 0x0FFFFFFF;  t = th << 6 | ts6
+//   any other type: no CD event, no state
+// The upper half of a word is laid out as an EVT 2.0 word, so the summary is S2 and the scan of
+// the chunk summaries is the EVT 2.0 one itself (evt_group_kernel<Evt2>, evt_carry_kernel<Evt2>:
+// no second copy of those kernels), with n counting mask bits.  The legacy layout stores the two halves exchanged; the kernels swap them on load.
+// int32 bounds: a chunk is 256 * 8 = 2048 words of <= 32 events = at most 65 536 events (2^16);
+// off_local within a group of 512 chunks is at most 512 * 65 536 = 2^25.
+struct Evt21 {
+    using Word = uint64_t;
+    using S = S2;
+    static constexpr int kPer = 8;  // 64 B per lane; no stored lane prefixes: the fold is recomputed
+    __device__ static int count(uint64_t w) { return (w >> 61) == 0 ? __popc((uint32_t)w) : 0; }  // events of a word
+    __device__ static void fold(S &s, uint64_t w) {
+        s.n += count(w);
+        if ((w >> 60) == 0x8u) s.th = (int32_t)((uint32_t)(w >> 32) & 0x0FFFFFFFu);
+    }
+};
+
 static_assert(sizeof(S3) == 32 && sizeof(S2) == 32, "summary = 32 B");
 static_assert(ECC_EVT_STATE_BYTES >= 32, "state holds one summary");
 
@@ -221,6 +247,34 @@ __device__ inline void load_words(const typename F::Word *__restrict__ words, in
     } else {
 #pragma unroll
         for (int e = 0; e < kPer; ++e) w[e] = e < nw ? (uint32_t)words[first + e] : 0u;
+    }
+}
+
+// The same for 64-bit words (EVT 2.1): lane l owns words [l*8, l*8 + 8) = 64 B, four 16-B loads
+// when the run is complete and 16-B aligned (the buffer itself is only 8-B aligned), word by
+// word otherwise.  Words past n_words read as 0 (a CD word with an empty mask: no event, no
+// state).  kSwap exchanges the halves of every word (the legacy layout).
+template <bool kSwap>
+__device__ inline void load_words64(const uint64_t *__restrict__ words, int64_t n_words, int64_t c,
+                                    uint64_t (&w)[Evt21::kPer]) {
+    constexpr int kPer = Evt21::kPer, kChunk = kThreads * kPer;
+    const int64_t first = c * kChunk + (int64_t)threadIdx.x * kPer;
+    const int64_t left = n_words - first;
+    const int nw = left <= 0 ? 0 : (left < kPer ? (int)left : kPer);
+    if (nw == kPer && ((reinterpret_cast<uintptr_t>(words + first) & 15u) == 0)) {
+#pragma unroll
+        for (int v = 0; v < kPer / 2; ++v) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(words + first + v * 2);
+            w[2 * v] = (uint64_t)q.x | (uint64_t)q.y << 32;
+            w[2 * v + 1] = (uint64_t)q.z | (uint64_t)q.w << 32;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < kPer; ++e) w[e] = e < nw ? words[first + e] : 0ull;
+    }
+    if constexpr (kSwap) {
+#pragma unroll
+        for (int e = 0; e < kPer; ++e) w[e] = w[e] << 32 | w[e] >> 32;
     }
 }
 
@@ -305,7 +359,7 @@ evt_group_kernel(const typename F::S *__restrict__ sums, int64_t n_chunks, typen
     const S ex = block_excl_scan<F, kGroup>(v, wtot, &tot);
     if (c < n_chunks) {
         carry_local[c] = ex;
-        off_local[c] = ex.n;  // < 512 chunks * 8192 words * 12 events
+        off_local[c] = ex.n;  // EVT 3.0: < 512 chunks * 8192 words * 12 events < 2^26; EVT 2.1: <= 512 * 2048 * 32 = 2^25
     }
     if (threadIdx.x == 0) gsum[blockIdx.x] = tot;
 }
@@ -434,54 +488,214 @@ evt_decode_kernel(const typename F::Word *__restrict__ words, int64_t n_words, c
     }
 }
 
+// ---- EVT 2.1 kernels -----------------------------------------------------------------------
+template <bool kSwap>
+__global__ void __launch_bounds__(kThreads)
+evt21_summary_kernel(const uint64_t *__restrict__ words, int64_t n_words, S2 *__restrict__ sums) {
+    __shared__ S2 wtot[kThreads / 64];
+    uint64_t w[Evt21::kPer];
+    load_words64<kSwap>(words, n_words, blockIdx.x, w);
+    S2 s = Evt2::identity();
+#pragma unroll
+    for (int e = 0; e < Evt21::kPer; ++e) Evt21::fold(s, w[e]);
+    S2 tot;
+    block_excl_scan<Evt2, kThreads>(s, wtot, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+// EVT 2.1 decode: lanes own output events, not words, so a run of full masks (256 events in one
+// lane's 64 B) costs every lane the same.  Per chunk:
+//   1. every lane counts the events of its 8 words and the words that have any ("live" words);
+//      one block scan of {th, n | live << 17} gives the lane's carried TIME_HIGH, its first
+//      event and its first live-word index (n < 2^17 and live <= 2048 share the int32);
+//   2. live words are staged compactly in LDS as {mask, upper half} and the TIME_HIGH in force;
+//      each sets the bit of its first event in a 65 536-bit map of the chunk's events, and the
+//      word that holds event 64 q records {its index, 64 q - its first event} in own[q];
+//   3. wave v takes the 64-event blocks q = v, v + 4, ...: lane j's event i = 64 q + j belongs to
+//      live word own[q] + popcount(map[q] bits 1..j), at rank j - (highest such bit) in its mask
+//      (or j + own[q]'s distance when no word starts in bits 1..j); a 5-step popcount bisection
+//      selects that set bit.  No search over the staged words, and no lane handles more than
+//      one event per block.  Stores go to base + i: coalesced by construction.
+// LDS: 16 KB words + 8 KB th + 8 KB map + 4 KB own = 36 KB (+ the scan's 128 B).
+template <bool kSwap>
+__global__ void __launch_bounds__(kThreads)
+evt21_decode_kernel(const uint64_t *__restrict__ words, int64_t n_words, const S2 *__restrict__ sums,
+                    const S2 *__restrict__ carry_local, const int32_t *__restrict__ off_local,
+                    const S2 *__restrict__ gcarry, const int64_t *__restrict__ goff, uint32_t *__restrict__ xy,
+                    int64_t *__restrict__ t, uint8_t *__restrict__ p, int64_t cap) {
+    constexpr int kPer = Evt21::kPer, kChunk = kThreads * kPer;
+    constexpr int kBlocks = kChunk * 32 / 64;  // 64-event blocks of a chunk's events
+    __shared__ S2 wtot[kThreads / 64];
+    __shared__ uint2 s_w[kChunk];               // live word k: {mask, upper half}
+    __shared__ uint32_t s_th[kChunk];           // TIME_HIGH in force at live word k
+    __shared__ unsigned long long s_map[kBlocks];  // bit i: a live word's first event is event i
+    __shared__ uint32_t s_own[kBlocks];         // live word holding event 64 q | (64 q - its first event) << 16
+    const int tid = threadIdx.x;
+    uint64_t w[kPer];
+    load_words64<kSwap>(words, n_words, blockIdx.x, w);
+#pragma unroll
+    for (int v = 0; v < kBlocks / kThreads; ++v) s_map[tid + v * kThreads] = 0ull;
+    int cnt[kPer];
+    S2 s = Evt2::identity();
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) {
+        cnt[e] = Evt21::count(w[e]);
+        s.n += cnt[e] + (cnt[e] ? 1 << 17 : 0);
+        if ((w[e] >> 60) == 0x8u) s.th = (int32_t)((uint32_t)(w[e] >> 32) & 0x0FFFFFFFu);
+    }
+    const S2 exl = block_excl_scan<Evt2, kThreads>(s, wtot, nullptr);  // its barriers also publish the zeroed map
+    const int g = blockIdx.x / kGroup;
+    const int n_chunk = sums[blockIdx.x].n;  // <= 65 536
+    const int32_t th_in = exl.th >= 0 ? exl.th : Evt2::cat(gcarry[g], carry_local[blockIdx.x]).th;
+    uint32_t th = th_in >= 0 ? (uint32_t)th_in : 0u;
+    int o = exl.n & 0x1FFFF, k = exl.n >> 17;  // first event, first live word of this lane
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) {
+        const uint32_t hi = (uint32_t)(w[e] >> 32);
+        if (cnt[e]) {
+            s_w[k] = make_uint2((uint32_t)w[e], hi);
+            s_th[k] = th;
+            atomicOr(&s_map[o >> 6], 1ull << (o & 63));
+            const int q = (o + 63) >> 6;
+            if (64 * q < o + cnt[e]) s_own[q] = (uint32_t)k | (uint32_t)(64 * q - o) << 16;
+            o += cnt[e];
+            ++k;
+        }
+        th = (hi >> 28) == 0x8u ? (hi & 0x0FFFFFFFu) : th;
+    }
+    __syncthreads();
+    const int64_t base = goff[g] + off_local[blockIdx.x];
+    const int j = tid & 63;
+    for (int i = tid; i < n_chunk; i += kThreads) {
+        const int q = i >> 6;
+        const unsigned long long starts = s_map[q] & (~0ull >> (63 - j)) & ~1ull;  // words starting at events 64 q + 1 .. i
+        const uint32_t own = s_own[q];
+        const int kk = (int)(own & 0xFFFFu) + __popcll(starts);
+        int r = starts ? j - (63 - __clzll(starts)) : j + (int)(own >> 16);  // rank of the event's bit in its mask
+        const uint2 cw = s_w[kk];
+        uint32_t m = cw.x, b = 0;
+#pragma unroll
+        for (int h = 16; h >= 1; h >>= 1) {  // the r-th set bit of m: halve by popcount
+            const int c = __popc(m & ((1u << h) - 1u));
+            const bool up = r >= c;
+            r -= up ? c : 0;
+            b += up ? h : 0;
+            m = up ? m >> h : m;
+        }
+        const int64_t at = base + i;
+        if (at < cap) {
+            if (xy) xy[at] = (((cw.y >> 11 & 0x7FFu) + b) & 0xFFFFu) | (cw.y & 0x7FFu) << 16;
+            if (t) t[at] = (int64_t)s_th[kk] << 6 | (int64_t)(cw.y >> 22 & 0x3Fu);
+            if (p) p[at] = (uint8_t)(cw.y >> 28);
+        }
+    }
+}
+
+// Host side of the three phases, shared by every format: the workspace of a call, and the scan of
+// the chunk summaries between a format's summary and decode kernels.
+template <class S>
+struct EvtWs {
+    int64_t n_chunks, n_groups;
+    S *sums, *carry_local, *gsum, *gcarry;
+    int32_t *off_local, *err;
+    int64_t *goff;
+    uint4 *lanepre;
+};
+
+// Carves sums | carry_local | off_local | gsum | gcarry | goff | lane prefixes out of the context's
+// workspace and clears the status word.  An empty buffer is answered here (*done): n_out = 0.
+template <class S>
+int evt_prepare(ecc_ctx *ctx, int64_t n_words, int chunk_words, bool lane_prefix, int64_t *n_out, hipStream_t s,
+                EvtWs<S> &w, bool *done) {
+    *done = true;
+    w.n_chunks = (n_words + chunk_words - 1) / chunk_words;
+    if (w.n_chunks > INT32_MAX) return ECC_ERR_INVALID;
+    w.n_groups = (w.n_chunks + kGroup - 1) / kGroup;
+    size_t o = 0;
+    auto carve = [&](size_t bytes) { const size_t at = o; o = ecc::align_up(o + bytes, 256); return at; };
+    const size_t o_sums = carve((size_t)w.n_chunks * sizeof(S)), o_cl = carve((size_t)w.n_chunks * sizeof(S));
+    const size_t o_ol = carve((size_t)w.n_chunks * 4), o_gs = carve((size_t)w.n_groups * sizeof(S));
+    const size_t o_gc = carve((size_t)w.n_groups * sizeof(S)), o_go = carve((size_t)w.n_groups * 8);
+    const size_t o_lp = carve(lane_prefix ? (size_t)w.n_chunks * kThreads * sizeof(uint4) : 16);
+    int rc = ecc::ws_reserve(ctx, o);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(ctx->ws);
+    w.sums = reinterpret_cast<S *>(ws + o_sums), w.carry_local = reinterpret_cast<S *>(ws + o_cl);
+    w.off_local = reinterpret_cast<int32_t *>(ws + o_ol);
+    w.gsum = reinterpret_cast<S *>(ws + o_gs), w.gcarry = reinterpret_cast<S *>(ws + o_gc);
+    w.goff = reinterpret_cast<int64_t *>(ws + o_go);
+    w.lanepre = reinterpret_cast<uint4 *>(ws + o_lp);
+    w.err = &ctx->dev->evt;
+    ECC_CHECK_HIP(ctx, hipMemsetAsync(w.err, 0, 4, s), "memset(evt err)");
+    if (w.n_chunks == 0) {
+        if (n_out) ECC_CHECK_HIP(ctx, hipMemsetAsync(n_out, 0, 8, s), "memset(n_out)");
+        return ECC_OK;
+    }
+    *done = false;
+    return ECC_OK;
+}
+
+// Phase 2 with format F's summaries (EVT 2.1 passes Evt2: same summary, same concatenation).
+template <class F>
+void evt_scan_chunks(ecc_ctx *ctx, const EvtWs<typename F::S> &w, void *state, int64_t *n_out, int64_t cap,
+                     hipStream_t s) {
+    using S = typename F::S;
+    {
+        ECC_TIMED(ctx, s, "evt_group_kernel");
+        hipLaunchKernelGGL(evt_group_kernel<F>, dim3((unsigned)w.n_groups), dim3(kGroup), 0, s, w.sums, w.n_chunks,
+                           w.carry_local, w.off_local, w.gsum);
+    }
+    {
+        ECC_TIMED(ctx, s, "evt_carry_kernel");
+        hipLaunchKernelGGL(evt_carry_kernel<F>, dim3(1), dim3(kGroup), 0, s, w.gsum, w.n_groups, w.gcarry, w.goff,
+                           static_cast<S *>(state), n_out, cap, w.err);
+    }
+}
+
+template <bool kSwap>
+int decode21(ecc_ctx *ctx, const void *words_v, int64_t n_words, uint32_t *xy, int64_t *t, uint8_t *p, int64_t cap,
+             int64_t *n_out, void *state, hipStream_t s) {
+    const auto *words = static_cast<const uint64_t *>(words_v);
+    EvtWs<S2> w;
+    bool done;
+    if (int rc = evt_prepare(ctx, n_words, kThreads * Evt21::kPer, false, n_out, s, w, &done)) return rc;
+    if (done) return ECC_OK;
+    {
+        ECC_TIMED(ctx, s, "evt21_summary_kernel");
+        hipLaunchKernelGGL(evt21_summary_kernel<kSwap>, dim3((unsigned)w.n_chunks), dim3(kThreads), 0, s, words, n_words,
+                           w.sums);
+    }
+    evt_scan_chunks<Evt2>(ctx, w, state, n_out, cap, s);
+    {
+        ECC_TIMED(ctx, s, "evt21_decode_kernel");
+        hipLaunchKernelGGL(evt21_decode_kernel<kSwap>, dim3((unsigned)w.n_chunks), dim3(kThreads), 0, s, words, n_words,
+                           (const S2 *)w.sums, (const S2 *)w.carry_local, (const int32_t *)w.off_local,
+                           (const S2 *)w.gcarry, (const int64_t *)w.goff, xy, t, p, cap);
+    }
+    ECC_CHECK_LAUNCH(ctx, "evt21 decode");
+    return ECC_OK;
+}
+
 template <class F>
 int decode(ecc_ctx *ctx, const void *words_v, int64_t n_words, uint32_t *xy, int64_t *t, uint8_t *p, int64_t cap,
            int64_t *n_out, void *state, hipStream_t s) {
     using S = typename F::S;
     const auto *words = static_cast<const typename F::Word *>(words_v);
-    constexpr int kChunk = kThreads * F::kPer;
-    const int64_t n_chunks = (n_words + kChunk - 1) / kChunk;
-    if (n_chunks > INT32_MAX) return ECC_ERR_INVALID;
-    const int64_t n_groups = (n_chunks + kGroup - 1) / kGroup;
-    // workspace: sums | carry_local | off_local | gsum | gcarry | goff | lane prefixes
-    size_t o = 0;
-    auto carve = [&](size_t bytes) { const size_t at = o; o = ecc::align_up(o + bytes, 256); return at; };
-    const size_t o_sums = carve((size_t)n_chunks * sizeof(S)), o_cl = carve((size_t)n_chunks * sizeof(S));
-    const size_t o_ol = carve((size_t)n_chunks * 4), o_gs = carve((size_t)n_groups * sizeof(S));
-    const size_t o_gc = carve((size_t)n_groups * sizeof(S)), o_go = carve((size_t)n_groups * 8);
-    const size_t o_lp = carve(F::kLanePrefix ? (size_t)n_chunks * kThreads * sizeof(uint4) : 16);
-    int rc = ecc::ws_reserve(ctx, o);
-    if (rc) return rc;
-    char *ws = static_cast<char *>(ctx->ws);
-    S *sums = reinterpret_cast<S *>(ws + o_sums), *carry_local = reinterpret_cast<S *>(ws + o_cl);
-    int32_t *off_local = reinterpret_cast<int32_t *>(ws + o_ol);
-    S *gsum = reinterpret_cast<S *>(ws + o_gs), *gcarry = reinterpret_cast<S *>(ws + o_gc);
-    int64_t *goff = reinterpret_cast<int64_t *>(ws + o_go);
-    uint4 *lanepre = reinterpret_cast<uint4 *>(ws + o_lp);
-    int32_t *err = &ctx->dev->evt;
-    ECC_CHECK_HIP(ctx, hipMemsetAsync(err, 0, 4, s), "memset(evt err)");
-    if (n_chunks == 0) {
-        if (n_out) ECC_CHECK_HIP(ctx, hipMemsetAsync(n_out, 0, 8, s), "memset(n_out)");
-        return ECC_OK;
-    }
+    EvtWs<S> w;
+    bool done;
+    if (int rc = evt_prepare(ctx, n_words, kThreads * F::kPer, F::kLanePrefix, n_out, s, w, &done)) return rc;
+    if (done) return ECC_OK;
     {
         ECC_TIMED(ctx, s, "evt_summary_kernel");
-        hipLaunchKernelGGL(evt_summary_kernel<F>, dim3((unsigned)n_chunks), dim3(kThreads), 0, s, words, n_words, sums, lanepre);
+        hipLaunchKernelGGL(evt_summary_kernel<F>, dim3((unsigned)w.n_chunks), dim3(kThreads), 0, s, words, n_words, w.sums,
+                           w.lanepre);
     }
-    {
-        ECC_TIMED(ctx, s, "evt_group_kernel");
-        hipLaunchKernelGGL(evt_group_kernel<F>, dim3((unsigned)n_groups), dim3(kGroup), 0, s, sums, n_chunks,
-                           carry_local, off_local, gsum);
-    }
-    {
-        ECC_TIMED(ctx, s, "evt_carry_kernel");
-        hipLaunchKernelGGL(evt_carry_kernel<F>, dim3(1), dim3(kGroup), 0, s, gsum, n_groups, gcarry, goff,
-                           static_cast<S *>(state), n_out, cap, err);
-    }
+    evt_scan_chunks<F>(ctx, w, state, n_out, cap, s);
     {
         ECC_TIMED(ctx, s, "evt_decode_kernel");
-        hipLaunchKernelGGL(evt_decode_kernel<F>, dim3((unsigned)n_chunks), dim3(kThreads), 0, s, words, n_words, sums,
-                           carry_local, off_local, gcarry, goff, (const uint4 *)lanepre, xy, t, p, cap);
+        hipLaunchKernelGGL(evt_decode_kernel<F>, dim3((unsigned)w.n_chunks), dim3(kThreads), 0, s, words, n_words,
+                           (const S *)w.sums, (const S *)w.carry_local, (const int32_t *)w.off_local, (const S *)w.gcarry,
+                           (const int64_t *)w.goff, (const uint4 *)w.lanepre, xy, t, p, cap);
     }
     ECC_CHECK_LAUNCH(ctx, "evt decode");
     return ECC_OK;
@@ -526,6 +740,8 @@ ECC_API int ecc_evt_decode(ecc_ctx *ctx, int32_t format, const void *words, int6
     hipStream_t s = ecc::as_stream(stream);
     if (format == ECC_RAW_EVT3) return decode<Evt3>(ctx, words, n_words, xy, t, p, cap, n_out, state, s);
     if (format == ECC_RAW_EVT2) return decode<Evt2>(ctx, words, n_words, xy, t, p, cap, n_out, state, s);
+    if (format == ECC_RAW_EVT21) return decode21<false>(ctx, words, n_words, xy, t, p, cap, n_out, state, s);
+    if (format == ECC_RAW_EVT21_LEGACY) return decode21<true>(ctx, words, n_words, xy, t, p, cap, n_out, state, s);
     return ECC_ERR_INVALID;
 }
 

@@ -822,7 +822,12 @@ def read_csv(path: str):
 
 
 EVT2, EVT3 = 2, 3
+EVT21, EVT21_LEGACY = 21, 22
 EVT_STATE_BYTES = 64
+
+
+def _word_dtype(fmt: int):
+    return np.uint32 if fmt == EVT2 else np.uint64 if fmt in (EVT21, EVT21_LEGACY) else np.uint16
 
 
 def raw_probe(path) -> RawInfo:
@@ -833,7 +838,7 @@ def raw_probe(path) -> RawInfo:
 
 def raw_read_words(path, info: RawInfo, first: int = 0, n: int | None = None) -> np.ndarray:
     n = info.n_words - first if n is None else n
-    out = np.empty(max(n, 0), np.uint32 if info.format == EVT2 else np.uint16)
+    out = np.empty(max(n, 0), _word_dtype(info.format))
     got = lib.ecc_raw_read_words(str(path).encode(), C.byref(info), first, n, out.ctypes.data)
     if got < 0:
         raise EccError(int(got), f"raw_read_words({path})")
@@ -841,13 +846,13 @@ def raw_read_words(path, info: RawInfo, first: int = 0, n: int | None = None) ->
 
 
 def evt_encode(fmt: int, xy, t, p) -> np.ndarray:
-    """RAW writer (ecc_evt_encode): events -> EVT 2.0 (u32) / EVT 3.0 (u16) words."""
+    """RAW writer (ecc_evt_encode): events -> EVT 2.0 (u32) / EVT 2.1 (u64) / EVT 3.0 (u16) words."""
     xy = np.ascontiguousarray(xy, np.uint32)
     t = np.ascontiguousarray(t, np.int64)
     p = np.ascontiguousarray(p, np.uint8)
     n = len(xy)
-    cap = 2 * n + 1 if fmt == EVT2 else 4 * n + 4 + (2 * int(t[-1] >> 24) if n else 0)
-    out = np.empty(max(cap, 1), np.uint32 if fmt == EVT2 else np.uint16)
+    cap = 2 * n + 1 if fmt in (EVT2, EVT21, EVT21_LEGACY) else 4 * n + 4 + (2 * int(t[-1] >> 24) if n else 0)
+    out = np.empty(max(cap, 1), _word_dtype(fmt))
     k = lib.ecc_evt_encode(fmt, xy.ctypes.data, t.ctypes.data, p.ctypes.data, n, out.ctypes.data, cap)
     if k < 0:
         raise EccError(int(k), "evt_encode")

@@ -181,7 +181,10 @@ std::vector<TrackedCorner> CornerTracker::updateTrackedCorners(const std::vector
 RawFileReader::RawFileReader(Context &ctx, const std::string &path, int64_t chunk_words)
     : ctx_(ctx), path_(path), chunk_(chunk_words > 0 ? chunk_words : int64_t(1) << 24) {
     check(ecc_raw_probe(path.c_str(), &info_), "ecc_raw_probe");
-    const int64_t max_events = chunk_ * (info_.format == ECC_RAW_EVT3 ? 12 : 1);  // <= 12 per VECT_12 word
+    // <= 12 events per VECT_12 word, 1 per EVT 2.0 word.  An EVT 2.1 word holds up to 32, which at
+    // the default chunk would be about 7 GB of buffers: next() sizes those from the chunk's true count.
+    const bool evt21 = info_.format == ECC_RAW_EVT21 || info_.format == ECC_RAW_EVT21_LEGACY;
+    const int64_t max_events = evt21 ? 0 : chunk_ * (info_.format == ECC_RAW_EVT3 ? 12 : 1);
     host_.resize((size_t)(chunk_ * info_.word_bytes));
     words_.reserve(host_.size());
     xy_.reserve((size_t)max_events * 4);
@@ -198,6 +201,22 @@ int64_t RawFileReader::next(const uint32_t **d_xy, const int64_t **d_t, const ui
     if (got == 0) return 0;
     pos_ += got;
     words_.upload(host_.data(), (size_t)(got * info_.word_bytes), ctx_.stream());
+    if (info_.format == ECC_RAW_EVT21 || info_.format == ECC_RAW_EVT21_LEGACY) {
+        // the chunk's event count: the mask bits of its CD words (type 0 / 1 in the upper half)
+        const int up = info_.format == ECC_RAW_EVT21 ? 1 : 0, lo = 1 - up;
+        int64_t events = 0;
+        for (int64_t i = 0; i < got; ++i) {
+            uint32_t half[2];
+            std::memcpy(half, host_.data() + 8 * i, 8);
+            if ((half[up] >> 29) == 0) events += __builtin_popcount(half[lo]);
+        }
+        if ((int64_t)p_.size() < events) {
+            ctx_.sync();  // the buffers may still be in use by work queued on the stream
+            xy_.reserve((size_t)events * 4);
+            t_.reserve((size_t)events * 8);
+            p_.reserve((size_t)events);
+        }
+    }
     const int64_t cap = (int64_t)p_.size();
     check(ecc_evt_decode(ctx_.get(), info_.format, words_.data(), got, xy_.as<uint32_t>(), t_.as<int64_t>(),
                          p_.as<uint8_t>(), cap, n_.as<int64_t>(), state_.data(), ctx_.stream()),

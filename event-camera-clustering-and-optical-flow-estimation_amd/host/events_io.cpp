@@ -1,5 +1,5 @@
 // Host-side event sources: deterministic synthetic streams, CSV event files and the RAW
-// (EVT 2.0 / EVT 3.0) file header + payload reader.
+// (EVT 2.0 / EVT 2.1 / EVT 3.0) file header + payload reader.
 //
 // The reference ingests events through Metavision's Camera::from_file(argv[1]) / live camera
 // callbacks (FCT/…group_track.cpp:756-765, 1073-1074) and its OPTICS driver reads "x,y,t,p" CSV
@@ -194,11 +194,29 @@ ECC_HOST_API int64_t ecc_read_csv(const char *path, uint32_t *xy, int64_t *t, ui
 
 // ---- RAW files (include/ecc.h §8) ----------------------------------------------------------
 // Header: lines starting with '%' up to "% end" (or the first line not starting with '%').
-// Recognised keys: "% evt 2.0|3.0", "% format EVT2|EVT3[;height=H;width=W]", "% geometry WxH".
+// Recognised keys: "% evt 2.0|2.1|3.0", "% format EVT2|EVT21|EVT3[;height=H;width=W]" (with
+// "endianness=legacy" for the legacy EVT 2.1 layout), "% geometry WxH".
+// The name is compared as a whole token, ended by ';', a space or the end of the line, so that
+// "EVT21" is never read as "EVT2" whatever the order of the comparisons.
 static int parse_format_name(const char *v) {
-    if (!std::strncmp(v, "EVT3", 4) || !std::strncmp(v, "evt3", 4) || !std::strncmp(v, "3.0", 3)) return ECC_RAW_EVT3;
-    if (!std::strncmp(v, "EVT2", 4) || !std::strncmp(v, "evt2", 4) || !std::strncmp(v, "2.0", 3)) return ECC_RAW_EVT2;
+    size_t len = 0;
+    while (v[len] && v[len] != ';' && v[len] != ' ' && v[len] != '\t' && v[len] != '\r' && v[len] != '\n') ++len;
+    auto is = [&](const char *name) { return std::strlen(name) == len && !std::strncmp(v, name, len); };
+    if (is("EVT3") || is("evt3") || is("3.0")) return ECC_RAW_EVT3;
+    if (is("EVT21") || is("evt21") || is("2.1")) return ECC_RAW_EVT21;
+    if (is("EVT2") || is("evt2") || is("2.0")) return ECC_RAW_EVT2;
     return ECC_RAW_UNKNOWN;
+}
+
+// True when the ';'-separated keys of a format line hold "endianness=legacy" as a whole key.
+static bool has_legacy_key(const char *v) {
+    static const char key[] = "endianness=legacy";
+    for (const char *s = v; (s = std::strstr(s, key)); s += sizeof(key) - 1) {
+        const char e = s[sizeof(key) - 1];
+        if ((s == v || s[-1] == ';' || s[-1] == ' ') && (e == 0 || e == ';' || e == ' ' || e == '\r' || e == '\n'))
+            return true;
+    }
+    return false;
 }
 
 ECC_HOST_API int ecc_raw_probe(const char *path, ecc_raw_info *info) {
@@ -207,6 +225,7 @@ ECC_HOST_API int ecc_raw_probe(const char *path, ecc_raw_info *info) {
     FILE *f = std::fopen(path, "rb");
     if (!f) return ECC_ERR_INVALID;
     int64_t pos = 0;
+    bool legacy = false;
     char line[1024];
     for (;;) {
         const int c = std::fgetc(f);
@@ -228,6 +247,7 @@ ECC_HOST_API int ecc_raw_probe(const char *path, ecc_raw_info *info) {
         } else if (!std::strncmp(v, "format ", 7)) {
             const int fmt = parse_format_name(v + 7);
             if (fmt) info->format = fmt;
+            legacy = legacy || has_legacy_key(v + 7);
             const char *h = std::strstr(v, "height="), *w = std::strstr(v, "width=");
             if (h) info->height = std::atoi(h + 7);
             if (w) info->width = std::atoi(w + 6);
@@ -243,7 +263,8 @@ ECC_HOST_API int ecc_raw_probe(const char *path, ecc_raw_info *info) {
     const int64_t size = (int64_t)std::ftell(f);
     std::fclose(f);
     if (info->format == ECC_RAW_UNKNOWN) return ECC_ERR_INVALID;
-    info->word_bytes = info->format == ECC_RAW_EVT2 ? 4 : 2;
+    if (info->format == ECC_RAW_EVT21 && legacy) info->format = ECC_RAW_EVT21_LEGACY;
+    info->word_bytes = info->format == ECC_RAW_EVT2 ? 4 : info->format == ECC_RAW_EVT3 ? 2 : 8;
     info->header_bytes = pos;
     info->n_words = size > pos ? (size - pos) / info->word_bytes : 0;
     return ECC_OK;
@@ -267,7 +288,10 @@ ECC_HOST_API int64_t ecc_raw_read_words(const char *path, const ecc_raw_info *in
 
 // RAW writer (include/ecc.h §8).  EVT 2.0: TIME_HIGH on every change of t >> 6.  EVT 3.0:
 // TIME_HIGH on every change of t >> 12 (with 0xFFF, 0 pairs per 2^24 loop crossed), TIME_LOW
-// on every change of t, ADDR_Y on every change of y, vector words for row runs.
+// on every change of t, ADDR_Y on every change of y, vector words for row runs.  EVT 2.1:
+// TIME_HIGH before the first CD word and before any CD word with another t >> 6; an event joins
+// the open CD word iff t, y, p and x >> 5 are the word's and x & 31 lies above its highest set
+// bit, so that decoding in ascending bit order returns the input order (at most 2n + 1 words).
 ECC_HOST_API int64_t ecc_evt_encode(int32_t format, const uint32_t *xy, const int64_t *t, const uint8_t *p,
                                     int64_t n, void *out, int64_t cap) {
     if (n < 0 || cap < 0 || (n > 0 && (!xy || !t || !p)) || (cap > 0 && !out)) return ECC_ERR_INVALID;
@@ -287,6 +311,39 @@ ECC_HOST_API int64_t ecc_evt_encode(int32_t format, const uint32_t *xy, const in
             if (k < cap) o[k] = ((uint32_t)(p[i] & 1u) << 28) | ((uint32_t)(t[i] & 63) << 22) | (x << 11) | y;
             ++k;
         }
+        return k;
+    }
+    if (format == ECC_RAW_EVT21 || format == ECC_RAW_EVT21_LEGACY) {
+        auto *o = static_cast<uint64_t *>(out);
+        auto put = [&](uint64_t w) {
+            if (k < cap) o[k] = format == ECC_RAW_EVT21_LEGACY ? (w << 32 | w >> 32) : w;
+            ++k;
+        };
+        int64_t last = -1;   // t >> 6 of the last TIME_HIGH emitted
+        uint64_t open = 0;   // the open CD word's upper half (type, ts6, x & ~31, y) << 32
+        uint32_t mask = 0;   // its valid bits; 0: no word open
+        int64_t open_t = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            if (i && t[i] < t[i - 1]) return ECC_ERR_UNSORTED_TIME;
+            if (t[i] < 0 || t[i] >> 34) return ECC_ERR_INVALID;
+            const uint64_t x = xy[i] & 0x7FFu, y = (xy[i] >> 16) & 0x7FFu;
+            const uint64_t head = ((uint64_t)(p[i] & 1u) << 60) | ((uint64_t)(t[i] & 63) << 54) | ((x & ~31ull) << 43) | (y << 32);
+            const uint32_t bit = 1u << (x & 31);
+            if (mask && t[i] == open_t && head == open && bit > mask) {  // bit > mask: above the highest set bit
+                mask |= bit;
+                continue;
+            }
+            if (mask) put(open | mask);
+            const int64_t th = t[i] >> 6;
+            if (th != last) {
+                put(0x8ull << 60 | (uint64_t)(th & 0x0FFFFFFF) << 32);
+                last = th;
+            }
+            open = head;
+            open_t = t[i];
+            mask = bit;
+        }
+        if (mask) put(open | mask);
         return k;
     }
     if (format != ECC_RAW_EVT3) return ECC_ERR_INVALID;

@@ -868,25 +868,48 @@ int64_t ecc_read_csv(const char *path, uint32_t *xy, int64_t *t, uint8_t *p, int
 int64_t ecc_count_csv(const char *path);
 
 /* ---------------------------------------------------------------------------------------
- * 8. Event ingest: Prophesee/Metavision RAW files (EVT 2.0 / EVT 3.0) and the reslicer.
+ * 8. Event ingest: Prophesee/Metavision RAW files (EVT 2.0 / EVT 2.1 / EVT 3.0) and the reslicer.
  * Reference: every host program opens its input with Metavision::Camera::from_file(argv[1])
  *   (FCT/…group_track.cpp:756-760, SMP/…opencl_store.cpp:336) and cuts the decoded stream
  *   with EventBufferReslicerAlgorithm make_n_events(16384) (FCT/…group_track.cpp:772-774) or
  *   make_n_us(50000) (DSA/…opencl_store.cpp:351).  Metavision/OpenEB is not vendored: the
- *   decoders restate the published EVT 2.0 / EVT 3.0 word formats,
- *   parity "unpinned" against OpenEB itself.
+ *   decoders restate the published EVT 2.0 / EVT 2.1 / EVT 3.0 word formats (DESIGN.md
+ *   §Ingest), parity "unpinned" against OpenEB itself (for EVT 2.1 the half order of the
+ *   legacy layout included).
  *
  * A RAW file is an ASCII header of lines starting with '%' (ended by "% end" or by the first
- * line not starting with '%'), then little-endian words: u32 for EVT 2.0, u16 for EVT 3.0.
- * The format comes from "% evt 2.0|3.0" or "% format EVT2|EVT3;height=H;width=W"; the
- * geometry from "% geometry WxH" or the format line's width/height keys.
+ * line not starting with '%'), then little-endian words: u32 for EVT 2.0, u64 for EVT 2.1,
+ * u16 for EVT 3.0.  The format comes from "% evt 2.0|2.1|3.0" or
+ * "% format EVT2|EVT21|EVT3;height=H;width=W" (whole tokens, ended by ';', a space or the end
+ * of the line: EVT21 is not EVT2); the key "endianness=legacy" in the format line selects the
+ * legacy EVT 2.1 layout; the geometry comes from "% geometry WxH" or the format line's
+ * width/height keys.
+ *
+ * EVT 2.1 words (64-bit, little-endian), type = w >> 60:
+ *   0x0 EVT_NEG / 0x1 EVT_POS   ts6 = w >> 54 & 0x3F, x = w >> 43 & 0x7FF (a multiple of 32 in
+ *                               real files), y = w >> 32 & 0x7FF, valid = w & 0xFFFFFFFF
+ *   0x8 EVT_TIME_HIGH           th = w >> 32 & 0x0FFFFFFF
+ *   0xA, 0xE, 0xF, any other    trigger / others / continued: no CD event, no state
+ * A CD word yields one event per set bit b of valid, in ascending b:
+ *   xy = ((x + b) & 0xFFFF) | y << 16 (no alignment assumed, no other masking: x = 2047 gives
+ *   x up to 2078), t = (int64) th << 6 | ts6, p = type.  th is 0 before the first
+ *   EVT_TIME_HIGH; a mask of 0 yields nothing; there is no time-loop handling (as in EVT 2.0).
+ * ECC_RAW_EVT21_LEGACY: early files store the two 32-bit halves of every word exchanged (the
+ *   half with type, ts6, x and y at the lower address); the only difference is that w is
+ *   formed as lo << 32 | hi.
  * ------------------------------------------------------------------------------------- */
-typedef enum ecc_raw_format { ECC_RAW_UNKNOWN = 0, ECC_RAW_EVT2 = 2, ECC_RAW_EVT3 = 3 } ecc_raw_format;
+typedef enum ecc_raw_format {
+    ECC_RAW_UNKNOWN = 0,
+    ECC_RAW_EVT2 = 2,
+    ECC_RAW_EVT3 = 3,
+    ECC_RAW_EVT21 = 21,
+    ECC_RAW_EVT21_LEGACY = 22
+} ecc_raw_format;
 
 typedef struct ecc_raw_info {
     int32_t format;        /* ecc_raw_format */
     int32_t width, height; /* 0 when the header does not say */
-    int32_t word_bytes;    /* 4 (EVT2) or 2 (EVT3) */
+    int32_t word_bytes;    /* 4 (EVT2), 8 (EVT21, EVT21_LEGACY) or 2 (EVT3) */
     int64_t header_bytes;  /* payload starts here */
     int64_t n_words;       /* whole words in the payload */
 } ecc_raw_info;
@@ -897,10 +920,17 @@ int ecc_raw_probe(const char *path, ecc_raw_info *info);
 int64_t ecc_raw_read_words(const char *path, const ecc_raw_info *info, int64_t first_word,
                            int64_t n, void *buf);
 
-/* Host: RAW writer — encodes events (x, y < 2048, non-decreasing t) into EVT 2.0 (u32) or
- * EVT 3.0 (u16) words; EVT 3.0 runs of >= 3 events with equal (t, y, p) and increasing x
- * within 12 px go out as VECT_BASE_X + VECT_12.  Returns the number of words (<= cap written)
- * or a negative status.  Word bound: EVT 2.0 2n + 1, EVT 3.0 4n + 2 * (t_last >> 24) + 4. */
+/* Host: RAW writer — encodes events (x, y < 2048, non-decreasing t) into EVT 2.0 (u32),
+ * EVT 2.1 (u64) or EVT 3.0 (u16) words; EVT 3.0 runs of >= 3 events with equal (t, y, p) and
+ * increasing x within 12 px go out as VECT_BASE_X + VECT_12.  Returns the number of words
+ * (<= cap written) or a negative status.  Word bound: EVT 2.0 2n + 1, EVT 2.1 2n + 1,
+ * EVT 3.0 4n + 2 * (t_last >> 24) + 4.
+ * EVT 2.1 (formats 21 and 22; 22 writes the halves of every word exchanged): input limits as
+ * for EVT 2.0, and 0 <= t < 2^34 (ECC_ERR_INVALID otherwise).  An event joins the open CD word
+ * iff it has the word's t, y and p, the same x >> 5, and x & 31 above the word's highest set
+ * bit (so decoding in ascending bit order gives back the input order); otherwise the word is
+ * flushed and a new one opened at x & ~31.  An EVT_TIME_HIGH word goes out at the start of a
+ * non-empty stream and before any CD word whose t >> 6 differs from the last one emitted. */
 int64_t ecc_evt_encode(int32_t format, const uint32_t *xy, const int64_t *t, const uint8_t *p, int64_t n,
                        void *out, int64_t cap);
 
@@ -910,11 +940,12 @@ int64_t ecc_evt_encode(int32_t format, const uint32_t *xy, const int64_t *t, con
 #define ECC_EVT_STATE_BYTES 64
 
 /* GPU: decodes n_words device-resident words (format ECC_RAW_EVT2: const uint32_t*,
- * ECC_RAW_EVT3: const uint16_t*) into CD events in stream order:
+ * ECC_RAW_EVT3: const uint16_t*, ECC_RAW_EVT21 / ECC_RAW_EVT21_LEGACY: const uint64_t*, 8-byte
+ * aligned) into CD events in stream order:
  *   xy[i] = x | y << 16, t[i] = timestamp (µs), p[i] = polarity (0 = OFF, 1 = ON).
  * Event words carry 11-bit x/y; EVT 3.0 vector words expand to one event per set mask bit at
- * x = base + bit.  EVT 3.0 timestamps are 24-bit; each decrease of TIME_HIGH adds 2^24
- * (one loop).  Trigger / OTHERS / CONTINUED words produce no CD event.  Events before the
+ * x = base + bit, EVT 2.1 words likewise (32-bit mask, table above).  EVT 3.0 timestamps
+ * are 24-bit; each decrease of TIME_HIGH adds 2^24 (one loop).  Trigger / OTHERS / CONTINUED words produce no CD event.  Events before the
  * first TIME_HIGH word take time-high 0.
  * *n_out (device int64) = number of events in the buffer; only the first `cap` are written
  * (ecc_evt_status reports ECC_ERR_CAPACITY when n_out > cap).  Any of xy/t/p may be NULL. */

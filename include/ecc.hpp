@@ -209,6 +209,9 @@ class TimeSurfaceCornerDetector {
 // RAW recording reader (the role of Metavision::Camera::from_file(argv[1]), FCT/…group_track.cpp
 // :756-760): the host streams payload words from disk, the GPU decodes them (ecc_evt_decode)
 // with the carry state between chunks, so a recording of any length decodes piecewise.
+// EVT 2.0, EVT 2.1 (both half orders) and EVT 3.0.  An EVT 2.1 word holds up to 32 events, so for
+// that format the event buffers grow to each chunk's true count (the mask bits of its CD words,
+// counted on the host) and are never sized from the 32-per-word bound.
 class RawFileReader {
   public:
     RawFileReader(Context &ctx, const std::string &path, int64_t chunk_words = int64_t(1) << 24);
